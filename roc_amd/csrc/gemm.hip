@@ -4,10 +4,11 @@
 //            A row-major, B passed PRE-TRANSPOSED as Bt[N,K] so both LDS
 //            stages are direct coalesced copies (no transpose writes).
 //            Replaces reference cublasSgemm fwd/dX (`linear_kernel.cu:76,227`).
-//  gemm_atb: C[Ka,N] += A[R,Ka]^T @ B[R,N]   (fp32 out, split-K atomics)
+//  gemm_atb: C[Ka,N] += A[R,Ka]^T @ B[R,N]   (fp32 out, ordered split-K)
 //            the weight-gradient GEMM (reference `linear_kernel.cu:220`,
 //            beta=1 accumulate); reduction dim R is the node count (~10^5-6),
-//            so blocks split R and atomically accumulate fp32 partials.
+//            so blocks split R into fp32 partial slabs, reduced in a
+//            fixed order (bit-reproducible).
 //
 // Element types: bf16 (mfma_f32_16x16x32_bf16, the flagship path) and
 // exact fp32 (mfma_f32_16x16x4f32 at the f32 vector rate — gfx950 has no
@@ -307,10 +308,43 @@ __device__ __forceinline__ f32x4 frag_mfma_tswz(
   }
 }
 
+// Split-K epilogue. With one split the block owns its C elements and
+// accumulates in place. With several, each split stores its partial tile
+// into its own [Ka*N] slab of `part` (every in-range element, zeros
+// included: the slab is uninitialised) and atb_reduce_kernel folds the
+// slabs into C in a fixed order, so dW is bit-identical from run to run
+// (fp32 atomics into C summed in arrival order, and Adam's normalised
+// step blew that rounding noise up to percents of the weights).
+__device__ __forceinline__ void atb_emit(float* __restrict__ C,
+                                         float* __restrict__ part,
+                                         int64_t idx, int64_t slab,
+                                         float v) {
+  if (part != nullptr) part[(int64_t)blockIdx.z * slab + idx] = v;
+  else if (v != 0.f) atomicAdd(&C[idx], v);  // sole writer of C[idx]
+}
+
+// C[e] += sum_z part[z][e], fixed order: 4 strided z-lanes, then a tree.
+constexpr int kRedE = 64, kRedZ = 4;
+__global__ __launch_bounds__(kRedE * kRedZ) void atb_reduce_kernel(
+    float* __restrict__ C, const float* __restrict__ part, int64_t slab,
+    int splitk) {
+  __shared__ float red[kRedZ][kRedE];
+  const int64_t e = (int64_t)blockIdx.x * kRedE + threadIdx.x;
+  float s = 0.f;
+  if (e < slab)
+    for (int z = threadIdx.y; z < splitk; z += kRedZ)
+      s += part[(int64_t)z * slab + e];
+  red[threadIdx.y][threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.y == 0 && e < slab)
+    C[e] += (red[0][threadIdx.x] + red[1][threadIdx.x]) +
+            (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
 template <typename ET, bool ALIGNED_A, bool ALIGNED_B>
 __global__ __launch_bounds__(kBlock) void gemm_atb_kernel(
     float* __restrict__ C, const ET* __restrict__ A, const ET* __restrict__ B,
-    int R, int Ka, int N, int rows_per_split) {
+    int R, int Ka, int N, int rows_per_split, float* __restrict__ part) {
   __shared__ ET at_lds[BKA * PADK];
   __shared__ ET bt_lds[BNW * PADK];
 
@@ -359,8 +393,8 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_kernel(
     for (int j = 0; j < 4; ++j) {
       const int i = i_blk + i_wave + khalf * 4 + j;
       const int n = n_blk + ni * 16 + l15;
-      if (i < Ka && n < N && acc[ni][j] != 0.f)
-        atomicAdd(&C[(int64_t)i * N + n], acc[ni][j]);
+      if (i < Ka && n < N)
+        atb_emit(C, part, (int64_t)i * N + n, (int64_t)Ka * N, acc[ni][j]);
     }
   }
 }
@@ -372,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_kernel(
 template <typename ET, bool ALIGNED_A, bool ALIGNED_B>
 __global__ __launch_bounds__(kBlock) void gemm_atb_wide_kernel(
     float* __restrict__ C, const ET* __restrict__ A, const ET* __restrict__ B,
-    int R, int Ka, int N, int rows_per_split) {
+    int R, int Ka, int N, int rows_per_split, float* __restrict__ part) {
   __shared__ ET at_lds[2 * BKA * PADK];
   __shared__ ET bt_lds[2 * BNW * PADK];
 
@@ -438,8 +472,9 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_wide_kernel(
       for (int j = 0; j < 4; ++j) {
         const int i = i_blk + mi * BKA + i_wave + khalf * 4 + j;
         const int n = n_blk + ni * 16 + l15;
-        if (i < Ka && n < N && acc[mi][ni][j] != 0.f)
-          atomicAdd(&C[(int64_t)i * N + n], acc[mi][ni][j]);
+        if (i < Ka && n < N)
+          atb_emit(C, part, (int64_t)i * N + n, (int64_t)Ka * N,
+                   acc[mi][ni][j]);
       }
     }
   }
@@ -447,13 +482,13 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_wide_kernel(
 
 template <typename ET>
 void launch_atb(float* c, const ET* a, const ET* b, int R, int Ka, int N,
-                hipStream_t s) {
+                hipStream_t s, const torch::TensorOptions& c_opts) {
   const bool wide = Ka >= 2 * BKA && N >= 2 * BNW;
   const int tw = wide ? 2 : 1;
   const int tiles = ((Ka + tw * BKA - 1) / (tw * BKA)) *
                     ((N + tw * BNW - 1) / (tw * BNW));
   // split-K count trades fill (tiles*splitk workgroups) against the
-  // atomic RMW volume into C (Ka*N*splitk adds); pinned once at first
+  // partial-slab volume (Ka*N*splitk stores + loads); pinned once at first
   // launch (same hipGraph-capture rule as the SpMM knobs)
   static const int splitk_env = [] {
     const char* e = getenv("ROC_ATB_SPLITK");
@@ -462,9 +497,18 @@ void launch_atb(float* c, const ET* a, const ET* b, int R, int Ka, int N,
   int splitk = splitk_env > 0 ? splitk_env : 2048 / max(tiles, 1);
   splitk = max(1, min(splitk, (R + RB - 1) / RB));
   const char* det = getenv("ROC_DETERMINISTIC");
-  if (det && det[0] == '1') splitk = 1;  // bit-reproducible dW (slower)
+  if (det && det[0] == '1') splitk = 1;  // single-pass dW (slower)
   int rows_per_split = ((R + splitk - 1) / splitk + RB - 1) / RB * RB;
   splitk = (R + rows_per_split - 1) / rows_per_split;
+  // one [Ka*N] slab per split; from torch's stream-ordered allocator, so
+  // it is safe on side streams and under hipGraph capture
+  const int64_t slab = (int64_t)Ka * N;
+  torch::Tensor part_t;
+  float* part = nullptr;
+  if (splitk > 1) {
+    part_t = torch::empty({(int64_t)splitk * slab}, c_opts);
+    part = part_t.data_ptr<float>();
+  }
   dim3 grid((Ka + tw * BKA - 1) / (tw * BKA),
             (N + tw * BNW - 1) / (tw * BNW), splitk);
   const bool ala = (Ka % GemmTraits<ET>::kEPS) == 0;
@@ -474,16 +518,21 @@ void launch_atb(float* c, const ET* a, const ET* b, int R, int Ka, int N,
     if (wide) {                                                               \
       hipLaunchKernelGGL((gemm_atb_wide_kernel<ET, ALA, ALB>), grid,          \
                          dim3(kBlock), 0, s, c, a, b, R, Ka, N,               \
-                         rows_per_split);                                     \
+                         rows_per_split, part);                               \
     } else {                                                                  \
       hipLaunchKernelGGL((gemm_atb_kernel<ET, ALA, ALB>), grid,               \
                          dim3(kBlock), 0, s, c, a, b, R, Ka, N,               \
-                         rows_per_split);                                     \
+                         rows_per_split, part);                               \
     }                                                                         \
   } while (0)
   if (ala) { if (alb) ROC_ATB_CASE(true, true); else ROC_ATB_CASE(true, false); }
   else     { if (alb) ROC_ATB_CASE(false, true); else ROC_ATB_CASE(false, false); }
 #undef ROC_ATB_CASE
+  if (part != nullptr) {
+    hipLaunchKernelGGL(atb_reduce_kernel,
+                       dim3((unsigned)((slab + kRedE - 1) / kRedE)),
+                       dim3(kRedE, kRedZ), 0, s, c, part, slab, splitk);
+  }
 }
 
 }  // namespace
@@ -544,10 +593,10 @@ void gemm_atb(torch::Tensor C, torch::Tensor A, torch::Tensor B) {
   if (A.scalar_type() == torch::kBFloat16) {
     launch_atb<unsigned short>(c, (const unsigned short*)A.data_ptr(),
                                (const unsigned short*)B.data_ptr(), R, Ka, N,
-                               s);
+                               s, C.options());
   } else if (A.scalar_type() == torch::kFloat32) {
     launch_atb<float>(c, A.data_ptr<float>(), B.data_ptr<float>(), R, Ka, N,
-                      s);
+                      s, C.options());
   } else {
     TORCH_CHECK(false, "gemm_atb: bf16 or fp32 only");
   }

@@ -4,8 +4,10 @@
 // equivalents are the C++ loader/partition code in `gnn.cc:751-872`.
 #include <torch/extension.h>
 
-#include <atomic>\n#include <cstdint>\n#include <unordered_map>
+#include <atomic>
+#include <cstdint>
 #include <cstring>
+#include <unordered_map>
 #include <vector>
 
 #ifdef _OPENMP

@@ -123,23 +123,30 @@ def test_sharded_training_matches_single_rank():
     assert abs(md["ce_loss"] - m_single["ce_loss"]) < 1e-3
 
 
-def test_bench_contract_ws2_gloo():
+def test_bench_contract_ws2_gloo(tmp_path):
     """The driver's scale run launches bench.py under torchrun with
     --gpus N: guard that contract end-to-end on CPU (gloo, ws=2) — one
-    JSON line on rank 0 with the whole-job metric fields."""
+    JSON line on rank 0 with the whole-job metric fields, exactly the
+    requested timed steps, and --dump-outputs leaving the last epoch's
+    metrics + weights as float32 .npy files."""
     import json
     import os
     import subprocess
     import sys
+    import numpy as np
     import roc_amd
+    dump = str(tmp_path / "dump")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(roc_amd.__file__)))
     env = dict(os.environ)
     env.pop("ROC_SPMM_SCHEDULE", None)
+    # private dataset cache: never meet another user's files in /tmp
+    env["ROC_BENCH_CACHE"] = str(tmp_path)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29737", os.path.join(repo, "bench.py"),
-         "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02"],
+         "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.02",
+         "--dump-outputs", dump],
         capture_output=True, text=True, timeout=600, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -148,6 +155,16 @@ def test_bench_contract_ws2_gloo():
     assert out["unit"] == "s/epoch" and out["value"] > 0
     assert out["higher_is_better"] is False
     assert "parallelism" in out["config"]
+    assert abs(out["ms_per_step"] - out["value"] * 1e3) < 1e-6
+    assert sorted(os.listdir(dump)) == [
+        "metrics.npy", "weights.0.npy", "weights.1.npy"]
+    for fn in os.listdir(dump):
+        a = np.load(os.path.join(dump, fn))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), fn
+    m = np.load(os.path.join(dump, "metrics.npy"))
+    # whole-job metrics: train+val+test totals cover every node once
+    n_nodes = out["config"]["global_batch"]
+    assert m.shape == (8,) and m[3] + m[5] + m[7] == n_nodes
 
 
 def _recompute_worker(rank, port, q):

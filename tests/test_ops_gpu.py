@@ -172,6 +172,32 @@ def test_gemm_atb(R, Ka, N):
         (got - want).abs().max()
 
 
+@pytest.mark.parametrize("R,Ka,N", [(3000, 256, 41),     # 64x64 tiles
+                                    (1500, 136, 129)])   # wide, ragged
+def test_gemm_atb_accumulates_reproducibly(R, Ka, N):
+    """Split-K dW is C += A^T B with the partials folded in a fixed
+    order: two calls on equal inputs give bit-identical results, and a
+    non-zero C is accumulated into, not overwritten. Inputs are bf16
+    (exact in fp32), products and sums fp32: the bound on the sum is the
+    reference test's, the one on reproducibility is exact."""
+    torch.manual_seed(16)
+    A = torch.randn(R, Ka).to(torch.bfloat16)
+    B = (torch.randn(R, N) * 0.1).to(torch.bfloat16)
+    C0 = torch.randn(Ka, N)
+    want = C0 + A.float().t() @ B.float()
+    Ad, Bd = A.to(DEV), B.to(DEV)
+    outs = []
+    for _ in range(2):
+        C = C0.to(DEV)
+        _ext().gemm_atb(C, Ad, Bd)
+        outs.append(C.cpu())
+    assert torch.equal(outs[0], outs[1]), \
+        (outs[0] - outs[1]).abs().max()
+    tol = want.abs().max().item() * 2 ** -7 + 1e-2
+    assert torch.allclose(outs[0], want, atol=tol, rtol=0.05), \
+        (outs[0] - want).abs().max()
+
+
 def test_linear_autograd_gpu():
     """Wiring test: backward grads must match a fp32 reference built from
     the GPU's OWN bf16 forward output (isolates kernel wiring from

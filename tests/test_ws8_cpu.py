@@ -59,10 +59,10 @@ def _single_rank_baseline():
     return tr.evaluate(), model.weights[0].detach()
 
 
-def test_bench_contract_ws8_gloo():
+def test_bench_contract_ws8_gloo(tmp_path):
     """The driver's largest scale point: torchrun ws=8 through bench.py
     end-to-end (gloo on CPU, tiny scale) — one JSON line, whole-job
-    metric, agreed auto-extended step count across 8 ranks."""
+    metric, exactly the requested step count on all 8 ranks."""
     import json
     import subprocess
     import sys
@@ -71,7 +71,8 @@ def test_bench_contract_ws8_gloo():
         roc_amd.__file__)))
     env = dict(os.environ)
     env.pop("ROC_SPMM_SCHEDULE", None)
-    env["ROC_BENCH_CACHE"] = env.get("TMPDIR", "/tmp")
+    # private dataset cache: never meet another user's files in /tmp
+    env["ROC_BENCH_CACHE"] = str(tmp_path)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
