@@ -3,6 +3,8 @@
 // fp32 accumulation over bf16 storage. No CUDA-compat shims.
 #pragma once
 
+#include <type_traits>
+
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -79,7 +81,15 @@ __device__ __forceinline__ void store_bf16x8(unsigned short* p,
   v.w = pack_bf16(a[6], a[7]);
   *reinterpret_cast<uint4*>(p) = v;
 }
-__device__ __forceinline__ void store_f32x8(float* p, const float* a) {
+// one accumulator unit -> one output unit, picked by (output type, width)
+__device__ __forceinline__ void store_vec(unsigned short* p,
+                                          const float (&a)[8]) {
+  store_bf16x8(p, a);
+}
+__device__ __forceinline__ void store_vec(float* p, const float (&a)[4]) {
+  store_f32x4(p, a);
+}
+__device__ __forceinline__ void store_vec(float* p, const float (&a)[8]) {
   store_f32x4(p, a);
   store_f32x4(p + 4, a + 4);
 }
@@ -100,4 +110,21 @@ inline int roc_grid_1d(long long work, int per_block, int cap = 4096) {
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (int)g;
+}
+
+// runtime -> compile-time dispatch for launchers: f receives a
+// std::true_type / std::false_type, or an EltTag naming the storage type
+template <typename F>
+void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+template <typename T>
+struct EltTag { using type = T; };
+
+template <typename F>
+void dispatch_elt(torch::ScalarType st, const char* op, F&& f) {
+  if (st == torch::kBFloat16) f(EltTag<unsigned short>{});
+  else if (st == torch::kFloat32) f(EltTag<float>{});
+  else TORCH_CHECK(false, op, ": unsupported dtype (bf16/f32 only)");
 }

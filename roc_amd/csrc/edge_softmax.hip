@@ -13,7 +13,7 @@
 // tensors, nothing consumes them); this + spmm_edge make a full
 // attention-style aggregation MI355X-native.
 
-#include "common.h"
+#include "row_team.h"
 
 namespace {
 
@@ -21,27 +21,21 @@ template <int TEAM>
 __global__ __launch_bounds__(kBlock) void edge_softmax_fwd_kernel(
     float* __restrict__ alpha, const float* __restrict__ s,
     const int64_t* __restrict__ rowptr, int num_rows) {
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
-  for (int row = team; row < num_rows; row += nteams) {
+  const RowTeam<TEAM> rt;
+  const int lane = rt.lane;
+  for (int row = rt.team; row < num_rows; row += rt.nteams) {
     const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
     if (e0 == e1) continue;
     float m = -3.4e38f;
     for (int64_t e = e0 + lane; e < e1; e += TEAM) m = fmaxf(m, s[e]);
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = team_reduce_max<TEAM>(m);
     float sum = 0.f;
     for (int64_t e = e0 + lane; e < e1; e += TEAM) {
       const float ex = __expf(s[e] - m);
       alpha[e] = ex;
       sum += ex;
     }
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      sum += __shfl_xor(sum, off, 64);
+    sum = team_reduce_sum<TEAM>(sum);
     const float inv = 1.f / sum;
     for (int64_t e = e0 + lane; e < e1; e += TEAM) alpha[e] *= inv;
   }
@@ -53,40 +47,46 @@ __global__ __launch_bounds__(kBlock) void edge_softmax_bwd_kernel(
     float* __restrict__ ds, const float* __restrict__ dalpha,
     const float* __restrict__ alpha, const int64_t* __restrict__ rowptr,
     int num_rows) {
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
-  for (int row = team; row < num_rows; row += nteams) {
+  const RowTeam<TEAM> rt;
+  const int lane = rt.lane;
+  for (int row = rt.team; row < num_rows; row += rt.nteams) {
     const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
     if (e0 == e1) continue;
     float dot = 0.f;
     for (int64_t e = e0 + lane; e < e1; e += TEAM)
       dot += alpha[e] * dalpha[e];
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      dot += __shfl_xor(dot, off, 64);
+    dot = team_reduce_sum<TEAM>(dot);
     for (int64_t e = e0 + lane; e < e1; e += TEAM)
       ds[e] = alpha[e] * (dalpha[e] - dot);
   }
+}
+
+constexpr int kSegTeam = 8;  // avg in-degree ~edges/rows; 8 lanes/row
+
+void check_f32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32,
+              name, " must be a contiguous fp32 GPU tensor");
+}
+
+// returns the row count
+int check_rowptr(const torch::Tensor& rowptr) {
+  ROC_CHECK_DEV_CONT(rowptr);
+  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr int64");
+  return (int)rowptr.numel() - 1;
 }
 
 }  // namespace
 
 void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
                       torch::Tensor rowptr) {
-  ROC_CHECK_DEV_CONT(alpha);
-  ROC_CHECK_DEV_CONT(s);
-  ROC_CHECK_DEV_CONT(rowptr);
-  TORCH_CHECK(s.scalar_type() == torch::kFloat32, "scores must be fp32");
+  check_f32(alpha, "alpha");
+  check_f32(s, "scores");
   TORCH_CHECK(alpha.numel() == s.numel(), "size mismatch");
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr int64");
-  const int num_rows = (int)rowptr.numel() - 1;
-  constexpr int TEAM = 8;  // avg in-degree ~edges/rows; 8 lanes/row
-  const int tpb = kBlock / TEAM;
-  hipLaunchKernelGGL((edge_softmax_fwd_kernel<TEAM>),
-                     dim3(roc_grid_1d(num_rows, tpb, 8192)), dim3(kBlock),
-                     0, roc_stream(), alpha.data_ptr<float>(),
+  const int num_rows = check_rowptr(rowptr);
+  hipLaunchKernelGGL((edge_softmax_fwd_kernel<kSegTeam>),
+                     row_team_grid(num_rows, kSegTeam), dim3(kBlock), 0,
+                     roc_stream(), alpha.data_ptr<float>(),
                      s.data_ptr<float>(), rowptr.data_ptr<int64_t>(),
                      num_rows);
   ROC_HIP_CHECK(hipGetLastError());
@@ -94,17 +94,15 @@ void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
 
 void edge_softmax_bwd(torch::Tensor ds, torch::Tensor dalpha,
                       torch::Tensor alpha, torch::Tensor rowptr) {
-  ROC_CHECK_DEV_CONT(ds);
-  ROC_CHECK_DEV_CONT(dalpha);
-  ROC_CHECK_DEV_CONT(alpha);
-  ROC_CHECK_DEV_CONT(rowptr);
-  TORCH_CHECK(ds.scalar_type() == torch::kFloat32, "grads must be fp32");
-  const int num_rows = (int)rowptr.numel() - 1;
-  constexpr int TEAM = 8;
-  const int tpb = kBlock / TEAM;
-  hipLaunchKernelGGL((edge_softmax_bwd_kernel<TEAM>),
-                     dim3(roc_grid_1d(num_rows, tpb, 8192)), dim3(kBlock),
-                     0, roc_stream(), ds.data_ptr<float>(),
+  check_f32(ds, "ds");
+  check_f32(dalpha, "dalpha");
+  check_f32(alpha, "alpha");
+  TORCH_CHECK(ds.numel() == alpha.numel() && dalpha.numel() == alpha.numel(),
+              "size mismatch");
+  const int num_rows = check_rowptr(rowptr);
+  hipLaunchKernelGGL((edge_softmax_bwd_kernel<kSegTeam>),
+                     row_team_grid(num_rows, kSegTeam), dim3(kBlock), 0,
+                     roc_stream(), ds.data_ptr<float>(),
                      dalpha.data_ptr<float>(), alpha.data_ptr<float>(),
                      rowptr.data_ptr<int64_t>(), num_rows);
   ROC_HIP_CHECK(hipGetLastError());
@@ -127,11 +125,9 @@ __global__ __launch_bounds__(kBlock) void att_softmax_fwd_kernel(
     float* __restrict__ alpha, const float* __restrict__ s_src,
     const float* __restrict__ s_dst, const int64_t* __restrict__ rowptr,
     const int* __restrict__ colidx, int num_rows, float slope) {
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
-  for (int row = team; row < num_rows; row += nteams) {
+  const RowTeam<TEAM> rt;
+  const int lane = rt.lane;
+  for (int row = rt.team; row < num_rows; row += rt.nteams) {
     const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
     if (e0 == e1) continue;
     const float sd = s_dst[row];
@@ -142,18 +138,14 @@ __global__ __launch_bounds__(kBlock) void att_softmax_fwd_kernel(
       alpha[e] = sc;  // stash raw score; normalized below
       m = fmaxf(m, sc);
     }
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = team_reduce_max<TEAM>(m);
     float sum = 0.f;
     for (int64_t e = e0 + lane; e < e1; e += TEAM) {
       const float ex = __expf(alpha[e] - m);
       alpha[e] = ex;
       sum += ex;
     }
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      sum += __shfl_xor(sum, off, 64);
+    sum = team_reduce_sum<TEAM>(sum);
     const float inv = 1.f / sum;
     for (int64_t e = e0 + lane; e < e1; e += TEAM) alpha[e] *= inv;
   }
@@ -168,11 +160,9 @@ __global__ __launch_bounds__(kBlock) void att_softmax_bwd_kernel(
     const float* __restrict__ s_src, const float* __restrict__ s_dst,
     const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
     int num_rows, float slope) {
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
-  for (int row = team; row < num_rows; row += nteams) {
+  const RowTeam<TEAM> rt;
+  const int lane = rt.lane;
+  for (int row = rt.team; row < num_rows; row += rt.nteams) {
     const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
     if (e0 == e1) {
       if (lane == 0 && e0 == e1) dsdst[row] = 0.f;
@@ -182,9 +172,7 @@ __global__ __launch_bounds__(kBlock) void att_softmax_bwd_kernel(
     float dot = 0.f;
     for (int64_t e = e0 + lane; e < e1; e += TEAM)
       dot += alpha[e] * dalpha[e];
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      dot += __shfl_xor(dot, off, 64);
+    dot = team_reduce_sum<TEAM>(dot);
     // 4-deep unrolled so the random s_src gathers queue (the rolled
     // version exposed one 4-B gather latency per edge — r2c16)
     float dd = 0.f;
@@ -221,11 +209,24 @@ __global__ __launch_bounds__(kBlock) void att_softmax_bwd_kernel(
       dd += dscore;
       atomicAdd(dsrc + u, dscore);
     }
-#pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1)
-      dd += __shfl_xor(dd, off, 64);
+    dd = team_reduce_sum<TEAM>(dd);
     if (lane == 0) dsdst[row] = dd;
   }
+}
+
+// the checks both directions share; returns the row count
+int check_att(const torch::Tensor& alpha, const torch::Tensor& s_src,
+              const torch::Tensor& s_dst, const torch::Tensor& rowptr,
+              const torch::Tensor& colidx) {
+  check_f32(alpha, "alpha");
+  check_f32(s_src, "s_src");
+  check_f32(s_dst, "s_dst");
+  ROC_CHECK_DEV_CONT(colidx);
+  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, "colidx int32");
+  TORCH_CHECK(alpha.numel() == colidx.numel(), "size mismatch");
+  const int num_rows = check_rowptr(rowptr);
+  TORCH_CHECK(s_dst.numel() == num_rows, "s_dst size mismatch");
+  return num_rows;
 }
 
 }  // namespace
@@ -233,21 +234,10 @@ __global__ __launch_bounds__(kBlock) void att_softmax_bwd_kernel(
 void att_softmax_fwd(torch::Tensor alpha, torch::Tensor s_src,
                      torch::Tensor s_dst, torch::Tensor rowptr,
                      torch::Tensor colidx, double slope) {
-  ROC_CHECK_DEV_CONT(alpha);
-  ROC_CHECK_DEV_CONT(s_src);
-  ROC_CHECK_DEV_CONT(s_dst);
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
-  TORCH_CHECK(s_src.scalar_type() == torch::kFloat32 &&
-              s_dst.scalar_type() == torch::kFloat32, "scores must be fp32");
-  TORCH_CHECK(alpha.numel() == colidx.numel(), "size mismatch");
-  const int num_rows = (int)rowptr.numel() - 1;
-  TORCH_CHECK(s_dst.numel() == num_rows, "s_dst size mismatch");
-  constexpr int TEAM = 8;
-  const int tpb = kBlock / TEAM;
-  hipLaunchKernelGGL((att_softmax_fwd_kernel<TEAM>),
-                     dim3(roc_grid_1d(num_rows, tpb, 8192)), dim3(kBlock),
-                     0, roc_stream(), alpha.data_ptr<float>(),
+  const int num_rows = check_att(alpha, s_src, s_dst, rowptr, colidx);
+  hipLaunchKernelGGL((att_softmax_fwd_kernel<kSegTeam>),
+                     row_team_grid(num_rows, kSegTeam), dim3(kBlock), 0,
+                     roc_stream(), alpha.data_ptr<float>(),
                      s_src.data_ptr<float>(), s_dst.data_ptr<float>(),
                      rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
                      num_rows, (float)slope);
@@ -259,18 +249,16 @@ void att_softmax_bwd(torch::Tensor dsrc, torch::Tensor dsdst,
                      torch::Tensor s_src, torch::Tensor s_dst,
                      torch::Tensor rowptr, torch::Tensor colidx,
                      double slope) {
-  ROC_CHECK_DEV_CONT(dsrc);
-  ROC_CHECK_DEV_CONT(dsdst);
-  ROC_CHECK_DEV_CONT(dalpha);
-  ROC_CHECK_DEV_CONT(alpha);
-  const int num_rows = (int)rowptr.numel() - 1;
+  const int num_rows = check_att(alpha, s_src, s_dst, rowptr, colidx);
+  check_f32(dsrc, "dsrc");
+  check_f32(dsdst, "dsdst");
+  check_f32(dalpha, "dalpha");
+  TORCH_CHECK(dalpha.numel() == alpha.numel(), "dalpha size mismatch");
   TORCH_CHECK(dsrc.numel() == s_src.numel(), "dsrc size mismatch");
   TORCH_CHECK(dsdst.numel() == num_rows, "dsdst size mismatch");
-  constexpr int TEAM = 8;
-  const int tpb = kBlock / TEAM;
-  hipLaunchKernelGGL((att_softmax_bwd_kernel<TEAM>),
-                     dim3(roc_grid_1d(num_rows, tpb, 8192)), dim3(kBlock),
-                     0, roc_stream(), dsrc.data_ptr<float>(),
+  hipLaunchKernelGGL((att_softmax_bwd_kernel<kSegTeam>),
+                     row_team_grid(num_rows, kSegTeam), dim3(kBlock), 0,
+                     roc_stream(), dsrc.data_ptr<float>(),
                      dsdst.data_ptr<float>(), dalpha.data_ptr<float>(),
                      alpha.data_ptr<float>(), s_src.data_ptr<float>(),
                      s_dst.data_ptr<float>(), rowptr.data_ptr<int64_t>(),

@@ -201,16 +201,18 @@ void launch_rr(ET* C, const ET* A, const ET* Bt, const float* row_scale,
                int M, int N, int K, bool relu, hipStream_t s) {
   dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
   const bool al = (K % GemmTraits<ET>::kEPS) == 0;  // row stride = K
-#define ROC_RR_CASE(RELU_, ALA)                                               \
-  hipLaunchKernelGGL((gemm_rr_kernel<ET, BN, RELU_, ALA, ALA>), grid,         \
-                     dim3(kBlock), 0, s, C, A, Bt, row_scale, M, N, K)
-  if (relu) { if (al) ROC_RR_CASE(true, true); else ROC_RR_CASE(true, false); }
-  else      { if (al) ROC_RR_CASE(false, true); else ROC_RR_CASE(false, false); }
-#undef ROC_RR_CASE
+  dispatch_bool(relu, [&](auto relu_c) {
+    dispatch_bool(al, [&](auto al_c) {
+      constexpr bool AL = decltype(al_c)::value;
+      hipLaunchKernelGGL(
+          (gemm_rr_kernel<ET, BN, decltype(relu_c)::value, AL, AL>), grid,
+          dim3(kBlock), 0, s, C, A, Bt, row_scale, M, N, K);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
-// gemm_atb (split-K weight-grad GEMM, fp32 atomic accumulate)
+// gemm_atb (split-K weight-grad GEMM, fp32 slabs reduced in a fixed order)
 // ---------------------------------------------------------------------------
 
 constexpr int BKA = 64;  // Ka tile (output rows)
@@ -221,7 +223,7 @@ constexpr int RB = 32;   // reduction rows per step
 //
 // bf16 swizzle: the plain [c][r] image puts every lane of a half-wave
 // on the same bank pair (column stride 64*PADK bytes for a fixed r is
-// 0 mod the 32 write banks), measured at 22% of gemm_atb_wide's wave
+// 0 mod the 32 write banks), measured at 22% of the 128x128 tile's wave
 // cycles in SQ_LDS_BANK_CONFLICT (profiles/r29). Storing row
 // r ^ ((cseg&3)<<3) spreads the 8 column-segment lanes over 4 bank
 // groups while keeping each khalf-read's 8 elements contiguous; the
@@ -341,15 +343,20 @@ __global__ __launch_bounds__(kRedE * kRedZ) void atb_reduce_kernel(
             (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-template <typename ET, bool ALIGNED_A, bool ALIGNED_B>
+// One block owns a (TW*64) x (TW*64) output tile, TW in {1, 2}; each wave
+// owns TW Ka row-groups (mi) x 4*TW N fragments (ni). The 128x128 tile
+// (TW = 2) re-reads A and B across tiles 4x less than the 64x64 one (A is
+// re-read per N-tile, B per Ka-tile — at [608,256] that is 2.3 GB/call vs
+// 1.16 GB; measured r2c20).
+template <typename ET, int TW, bool ALIGNED_A, bool ALIGNED_B>
 __global__ __launch_bounds__(kBlock) void gemm_atb_kernel(
     float* __restrict__ C, const ET* __restrict__ A, const ET* __restrict__ B,
     int R, int Ka, int N, int rows_per_split, float* __restrict__ part) {
-  __shared__ ET at_lds[BKA * PADK];
-  __shared__ ET bt_lds[BNW * PADK];
+  __shared__ ET at_lds[TW * BKA * PADK];
+  __shared__ ET bt_lds[TW * BNW * PADK];
 
-  const int i_blk = blockIdx.x * BKA;
-  const int n_blk = blockIdx.y * BNW;
+  const int i_blk = blockIdx.x * (TW * BKA);
+  const int n_blk = blockIdx.y * (TW * BNW);
   const int r_begin = blockIdx.z * rows_per_split;
   const int r_end = min(R, r_begin + rows_per_split);
 
@@ -357,105 +364,42 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_kernel(
   const int lane = threadIdx.x & 63;
   const int l15 = lane & 15;
   const int khalf = lane >> 4;
-  const int i_wave = wave * 16;  // 16 Ka rows per wave
+  const int i_wave = wave * 16;  // 16 Ka rows per wave and row-group
 
-  f32x4 acc[4];
+  f32x4 acc[TW][4 * TW];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = {0.f, 0.f, 0.f, 0.f};
+  for (int mi = 0; mi < TW; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4 * TW; ++ni) acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
 
-  // T14 split pipeline: chunk r0+RB's global loads are issued right
-  // after the barrier, a full MFMA phase before their s_waitcnt in
-  // stage_writeT (the fused stage had zero latency hiding)
-  typename GemmTraits<ET>::Seg ra[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  typename GemmTraits<ET>::Seg rb[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  stage_loadT<ET, ALIGNED_A>(ra, A, r_begin, r_end, Ka, i_blk, Ka);
-  stage_loadT<ET, ALIGNED_B>(rb, B, r_begin, r_end, N, n_blk, N);
+  // T14 split pipeline: chunk r0+RB's global loads (2*TW tile loads) are
+  // issued right after the barrier, a full MFMA phase before their
+  // s_waitcnt in stage_writeT (the fused stage had zero latency hiding)
+  typename GemmTraits<ET>::Seg ra[TW][RB * 64 / kBlock / GemmTraits<ET>::kEPS];
+  typename GemmTraits<ET>::Seg rb[TW][RB * 64 / kBlock / GemmTraits<ET>::kEPS];
+  auto load_chunk = [&](int r0) {
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+      stage_loadT<ET, ALIGNED_A>(ra[t], A, r0, r_end, Ka, i_blk + t * BKA, Ka);
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+      stage_loadT<ET, ALIGNED_B>(rb[t], B, r0, r_end, N, n_blk + t * BNW, N);
+  };
+  load_chunk(r_begin);
   for (int r0 = r_begin; r0 < r_end; r0 += RB) {
-    stage_writeT<ET>(at_lds, ra);
-    stage_writeT<ET>(bt_lds, rb);
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+      stage_writeT<ET>(at_lds + t * BKA * PADK, ra[t]);
+#pragma unroll
+    for (int t = 0; t < TW; ++t)
+      stage_writeT<ET>(bt_lds + t * BNW * PADK, rb[t]);
     __syncthreads();
-    if (r0 + RB < r_end) {
-      stage_loadT<ET, ALIGNED_A>(ra, A, r0 + RB, r_end, Ka, i_blk, Ka);
-      stage_loadT<ET, ALIGNED_B>(rb, B, r0 + RB, r_end, N, n_blk, N);
-    }
+    if (r0 + RB < r_end) load_chunk(r0 + RB);
     const int irow = i_wave + l15;
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      acc[ni] = frag_mfma_tswz<ET>(at_lds, bt_lds, irow, ni * 16 + l15,
-                                   khalf, acc[ni]);
-    }
-    __syncthreads();
-  }
-
+    for (int mi = 0; mi < TW; ++mi) {
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = i_blk + i_wave + khalf * 4 + j;
-      const int n = n_blk + ni * 16 + l15;
-      if (i < Ka && n < N)
-        atb_emit(C, part, (int64_t)i * N + n, (int64_t)Ka * N, acc[ni][j]);
-    }
-  }
-}
-
-// 128x128 output-tile variant: 4x fewer cross-tile re-reads of A and B
-// (the 64x64 kernel re-read A per N-tile and B per Ka-tile — at
-// [608,256] that is 2.3 GB/call vs 1.16 GB here; measured r2c20).
-// Each wave owns 2 Ka row-groups (mi) x 8 N fragments (ni).
-template <typename ET, bool ALIGNED_A, bool ALIGNED_B>
-__global__ __launch_bounds__(kBlock) void gemm_atb_wide_kernel(
-    float* __restrict__ C, const ET* __restrict__ A, const ET* __restrict__ B,
-    int R, int Ka, int N, int rows_per_split, float* __restrict__ part) {
-  __shared__ ET at_lds[2 * BKA * PADK];
-  __shared__ ET bt_lds[2 * BNW * PADK];
-
-  const int i_blk = blockIdx.x * (2 * BKA);
-  const int n_blk = blockIdx.y * (2 * BNW);
-  const int r_begin = blockIdx.z * rows_per_split;
-  const int r_end = min(R, r_begin + rows_per_split);
-
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x & 63;
-  const int l15 = lane & 15;
-  const int khalf = lane >> 4;
-  const int i_wave = wave * 16;
-
-  f32x4 acc[2][8];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 8; ++ni) acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
-
-  // T14 split pipeline (see gemm_atb_kernel): 4 tile loads in flight
-  // across each MFMA phase
-  typename GemmTraits<ET>::Seg ra0[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  typename GemmTraits<ET>::Seg ra1[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  typename GemmTraits<ET>::Seg rb0[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  typename GemmTraits<ET>::Seg rb1[RB * 64 / kBlock / GemmTraits<ET>::kEPS];
-  stage_loadT<ET, ALIGNED_A>(ra0, A, r_begin, r_end, Ka, i_blk, Ka);
-  stage_loadT<ET, ALIGNED_A>(ra1, A, r_begin, r_end, Ka, i_blk + BKA, Ka);
-  stage_loadT<ET, ALIGNED_B>(rb0, B, r_begin, r_end, N, n_blk, N);
-  stage_loadT<ET, ALIGNED_B>(rb1, B, r_begin, r_end, N, n_blk + BNW, N);
-  for (int r0 = r_begin; r0 < r_end; r0 += RB) {
-    stage_writeT<ET>(at_lds, ra0);
-    stage_writeT<ET>(at_lds + BKA * PADK, ra1);
-    stage_writeT<ET>(bt_lds, rb0);
-    stage_writeT<ET>(bt_lds + BNW * PADK, rb1);
-    __syncthreads();
-    if (r0 + RB < r_end) {
-      stage_loadT<ET, ALIGNED_A>(ra0, A, r0 + RB, r_end, Ka, i_blk, Ka);
-      stage_loadT<ET, ALIGNED_A>(ra1, A, r0 + RB, r_end, Ka, i_blk + BKA,
-                                 Ka);
-      stage_loadT<ET, ALIGNED_B>(rb0, B, r0 + RB, r_end, N, n_blk, N);
-      stage_loadT<ET, ALIGNED_B>(rb1, B, r0 + RB, r_end, N, n_blk + BNW,
-                                 N);
-    }
-    const int irow = i_wave + l15;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int ni = 0; ni < 8; ++ni) {
+      for (int ni = 0; ni < 4 * TW; ++ni) {
         acc[mi][ni] = frag_mfma_tswz<ET>(at_lds + mi * BKA * PADK, bt_lds,
                                          irow, ni * 16 + l15, khalf,
                                          acc[mi][ni]);
@@ -465,9 +409,9 @@ __global__ __launch_bounds__(kBlock) void gemm_atb_wide_kernel(
   }
 
 #pragma unroll
-  for (int mi = 0; mi < 2; ++mi) {
+  for (int mi = 0; mi < TW; ++mi) {
 #pragma unroll
-    for (int ni = 0; ni < 8; ++ni) {
+    for (int ni = 0; ni < 4 * TW; ++ni) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int i = i_blk + mi * BKA + i_wave + khalf * 4 + j;
@@ -513,21 +457,17 @@ void launch_atb(float* c, const ET* a, const ET* b, int R, int Ka, int N,
             (N + tw * BNW - 1) / (tw * BNW), splitk);
   const bool ala = (Ka % GemmTraits<ET>::kEPS) == 0;
   const bool alb = (N % GemmTraits<ET>::kEPS) == 0;
-#define ROC_ATB_CASE(ALA, ALB)                                                \
-  do {                                                                        \
-    if (wide) {                                                               \
-      hipLaunchKernelGGL((gemm_atb_wide_kernel<ET, ALA, ALB>), grid,          \
-                         dim3(kBlock), 0, s, c, a, b, R, Ka, N,               \
-                         rows_per_split, part);                               \
-    } else {                                                                  \
-      hipLaunchKernelGGL((gemm_atb_kernel<ET, ALA, ALB>), grid,               \
-                         dim3(kBlock), 0, s, c, a, b, R, Ka, N,               \
-                         rows_per_split, part);                               \
-    }                                                                         \
-  } while (0)
-  if (ala) { if (alb) ROC_ATB_CASE(true, true); else ROC_ATB_CASE(true, false); }
-  else     { if (alb) ROC_ATB_CASE(false, true); else ROC_ATB_CASE(false, false); }
-#undef ROC_ATB_CASE
+  dispatch_bool(wide, [&](auto wide_c) {
+    dispatch_bool(ala, [&](auto ala_c) {
+      dispatch_bool(alb, [&](auto alb_c) {
+        hipLaunchKernelGGL(
+            (gemm_atb_kernel<ET, decltype(wide_c)::value ? 2 : 1,
+                             decltype(ala_c)::value, decltype(alb_c)::value>),
+            grid, dim3(kBlock), 0, s, c, a, b, R, Ka, N, rows_per_split,
+            part);
+      });
+    });
+  });
   if (part != nullptr) {
     hipLaunchKernelGGL(atb_reduce_kernel,
                        dim3((unsigned)((slab + kRedE - 1) / kRedE)),
@@ -559,21 +499,14 @@ void gemm_rr(torch::Tensor C, torch::Tensor A, torch::Tensor Bt, bool relu,
                 "row_scale must be fp32 [M]");
     rs = row_scale->data_ptr<float>();
   }
-  if (A.scalar_type() == torch::kBFloat16) {
-    auto* c = (unsigned short*)C.data_ptr();
-    auto* a = (const unsigned short*)A.data_ptr();
-    auto* b = (const unsigned short*)Bt.data_ptr();
-    if (N > 64) launch_rr<unsigned short, 128>(c, a, b, rs, M, N, K, relu, s);
-    else        launch_rr<unsigned short, 64>(c, a, b, rs, M, N, K, relu, s);
-  } else if (A.scalar_type() == torch::kFloat32) {
-    auto* c = C.data_ptr<float>();
-    auto* a = A.data_ptr<float>();
-    auto* b = Bt.data_ptr<float>();
-    if (N > 64) launch_rr<float, 128>(c, a, b, rs, M, N, K, relu, s);
-    else        launch_rr<float, 64>(c, a, b, rs, M, N, K, relu, s);
-  } else {
-    TORCH_CHECK(false, "gemm_rr: bf16 or fp32 only");
-  }
+  dispatch_elt(A.scalar_type(), "gemm_rr", [&](auto et) {
+    using ET = typename decltype(et)::type;
+    auto* c = (ET*)C.data_ptr();
+    auto* a = (const ET*)A.data_ptr();
+    auto* b = (const ET*)Bt.data_ptr();
+    if (N > 64) launch_rr<ET, 128>(c, a, b, rs, M, N, K, relu, s);
+    else        launch_rr<ET, 64>(c, a, b, rs, M, N, K, relu, s);
+  });
   ROC_HIP_CHECK(hipGetLastError());
 }
 
@@ -589,16 +522,10 @@ void gemm_atb(torch::Tensor C, torch::Tensor A, torch::Tensor B) {
   TORCH_CHECK(C.size(0) == Ka && C.size(1) == N, "gemm_atb: C shape");
   if (R == 0 || Ka == 0 || N == 0) return;  // empty partition: C += 0
   auto s = roc_stream();
-  auto* c = C.data_ptr<float>();
-  if (A.scalar_type() == torch::kBFloat16) {
-    launch_atb<unsigned short>(c, (const unsigned short*)A.data_ptr(),
-                               (const unsigned short*)B.data_ptr(), R, Ka, N,
-                               s, C.options());
-  } else if (A.scalar_type() == torch::kFloat32) {
-    launch_atb<float>(c, A.data_ptr<float>(), B.data_ptr<float>(), R, Ka, N,
-                      s, C.options());
-  } else {
-    TORCH_CHECK(false, "gemm_atb: bf16 or fp32 only");
-  }
+  dispatch_elt(A.scalar_type(), "gemm_atb", [&](auto et) {
+    using ET = typename decltype(et)::type;
+    launch_atb<ET>(C.data_ptr<float>(), (const ET*)A.data_ptr(),
+                   (const ET*)B.data_ptr(), R, Ka, N, s, C.options());
+  });
   ROC_HIP_CHECK(hipGetLastError());
 }

@@ -1,14 +1,16 @@
 // CSR SpMM neighbor aggregation for CDNA4 — the hot GNN op.
 //
-// out[v, :] = (deg_dst[v] *) sum_{e in row v} (deg_src[u_e] *) x[u_e, :]
+// out[v, :] = (deg_dst[v] *) sum_{e in row v} (w_e *) x[u_e, :]
+// with w_e one of: nothing, deg_src[u_e] (per source), edge_val[e] (per
+// edge) — one kernel body, the weight source is a compile-time policy.
 //
 // MI355X-native design (vs reference `scattergather_kernel.cu:20-76`,
 // which staged the full graph tensor host->FB per task and used
 // cub-scan + LDS atomics):
 //  - features stay HBM/L3-resident; no host staging
-//  - a "row team" of TEAM lanes owns one row at a time; each lane
-//    accumulates EPU output elements in registers (no LDS, no atomics)
-//  - 16-B vectorized gathers (uint4 of 8 bf16 / float4), 4-deep unrolled
+//  - a "row team" of TEAM lanes owns one row at a time (row_team.h); each
+//    lane accumulates EPU output elements in registers (no LDS, no atomics)
+//  - 16-B vectorized gathers (uint4 of 8 bf16 / float4), up to 16 in flight
 //  - optional fused degree scaling (deg_* are precomputed factors); the
 //    fast GCN path pre-scales sources in the GEMM epilogue so only the
 //    cheap per-row dst factor remains here
@@ -24,7 +26,7 @@
 // Backward runs this same kernel on the transpose CSR (exact on
 // asymmetric graphs; the reference assumed symmetry).
 
-#include "common.h"
+#include "row_team.h"
 
 namespace {
 
@@ -80,119 +82,81 @@ struct BufferGather {
   }
 };
 
-// hot path: this lane's 16-B unit is entirely inside D.
-// SRC is compile-time: the fused GCN path has no per-edge source scale,
-// and dropping the dead deg_src lookups frees the 8 index registers
-// (they otherwise stay live across all 8 in-flight gathers).
-template <typename T, int EPU, int UN, bool SRC, typename LD>
+// One rung of the unroll ladder: read N column indices, issue N gathers
+// into statically indexed slots (fully unrolled, so nothing is scratch),
+// then hand the payloads to `use(i, u_i, r_i)` in ascending edge order.
+template <int N, typename T, typename LD, typename USE>
+__device__ __forceinline__ void gather_group(
+    const LD& ld, const int* __restrict__ colidx, int64_t e, USE&& use) {
+  int u[N];
+  typename RawVec<T>::type r[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) u[i] = colidx[e + i];
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = ld.load(u[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) use(i, u[i], r[i]);
+}
+
+// Where the per-gather weight comes from. It is compile-time because the
+// fused GCN path has none: kNone must stay a plain add, and dropping the
+// dead deg_src lookups frees the index registers (they otherwise stay
+// live across all in-flight gathers).
+enum class Weight { kNone, kSrc, kEdge };  // 1 | w[u_e] | w[e]
+
+// acc += w_e * x[u_e, unit] for N consecutive edges. Per-edge weights are
+// sequential, so they load before the gathers issue (one scalar broadcast
+// per gather); per-source weights are looked up as the payloads land.
+template <int N, typename T, Weight W, typename LD>
+__device__ __forceinline__ void accum_group(
+    float* __restrict__ acc, const LD& ld, const int* __restrict__ colidx,
+    const float* __restrict__ weight, int64_t e) {
+  float w[N];
+  if constexpr (W == Weight::kEdge) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = weight[e + i];
+  }
+  gather_group<N, T>(ld, colidx, e,
+                     [&](int i, int u, const typename RawVec<T>::type& r) {
+    if constexpr (W == Weight::kEdge) acc_add(acc, r, w[i]);
+    else if constexpr (W == Weight::kSrc) acc_add(acc, r, weight[u]);
+    else acc_add(acc, r, 1.f);
+  });
+}
+
+// hot path: this lane's 16-B unit is entirely inside the column window.
+// The ladder keeps UN gathers in flight, then steps down; within a row
+// the accumulation order is always ascending in e.
+template <typename T, int UN, Weight W, typename LD>
 __device__ __forceinline__ void row_accum_vec(
-    float* __restrict__ acc, const LD& ld,
-    const int* __restrict__ colidx, const float* __restrict__ deg_src,
-    int64_t e0, int64_t e1) {
-  using Raw = typename RawVec<T>::type;
-  int64_t e = e0;
-  if (UN >= 16) {
-    // 16 in flight: two 8-groups issued back-to-back
-    for (; e + 15 < e1; e += 16) {
-      const int u0 = colidx[e], u1 = colidx[e + 1];
-      const int u2 = colidx[e + 2], u3 = colidx[e + 3];
-      const int u4 = colidx[e + 4], u5 = colidx[e + 5];
-      const int u6 = colidx[e + 6], u7 = colidx[e + 7];
-      const int v0 = colidx[e + 8], v1 = colidx[e + 9];
-      const int v2 = colidx[e + 10], v3 = colidx[e + 11];
-      const int v4 = colidx[e + 12], v5 = colidx[e + 13];
-      const int v6 = colidx[e + 14], v7 = colidx[e + 15];
-      const Raw r0 = ld.load(u0), r1 = ld.load(u1);
-      const Raw r2 = ld.load(u2), r3 = ld.load(u3);
-      const Raw r4 = ld.load(u4), r5 = ld.load(u5);
-      const Raw r6 = ld.load(u6), r7 = ld.load(u7);
-      const Raw s0 = ld.load(v0), s1 = ld.load(v1);
-      const Raw s2 = ld.load(v2), s3 = ld.load(v3);
-      const Raw s4 = ld.load(v4), s5 = ld.load(v5);
-      const Raw s6 = ld.load(v6), s7 = ld.load(v7);
-      if (SRC) {
-        acc_add(acc, r0, deg_src[u0]); acc_add(acc, r1, deg_src[u1]);
-        acc_add(acc, r2, deg_src[u2]); acc_add(acc, r3, deg_src[u3]);
-        acc_add(acc, r4, deg_src[u4]); acc_add(acc, r5, deg_src[u5]);
-        acc_add(acc, r6, deg_src[u6]); acc_add(acc, r7, deg_src[u7]);
-        acc_add(acc, s0, deg_src[v0]); acc_add(acc, s1, deg_src[v1]);
-        acc_add(acc, s2, deg_src[v2]); acc_add(acc, s3, deg_src[v3]);
-        acc_add(acc, s4, deg_src[v4]); acc_add(acc, s5, deg_src[v5]);
-        acc_add(acc, s6, deg_src[v6]); acc_add(acc, s7, deg_src[v7]);
-      } else {
-        acc_add(acc, r0, 1.f); acc_add(acc, r1, 1.f);
-        acc_add(acc, r2, 1.f); acc_add(acc, r3, 1.f);
-        acc_add(acc, r4, 1.f); acc_add(acc, r5, 1.f);
-        acc_add(acc, r6, 1.f); acc_add(acc, r7, 1.f);
-        acc_add(acc, s0, 1.f); acc_add(acc, s1, 1.f);
-        acc_add(acc, s2, 1.f); acc_add(acc, s3, 1.f);
-        acc_add(acc, s4, 1.f); acc_add(acc, s5, 1.f);
-        acc_add(acc, s6, 1.f); acc_add(acc, s7, 1.f);
-      }
-    }
-  }
-  if (UN >= 8) {
-    // 8 in flight (raw payloads, unpack at use)
-    for (; e + 7 < e1; e += 8) {
-      const int u0 = colidx[e], u1 = colidx[e + 1];
-      const int u2 = colidx[e + 2], u3 = colidx[e + 3];
-      const int u4 = colidx[e + 4], u5 = colidx[e + 5];
-      const int u6 = colidx[e + 6], u7 = colidx[e + 7];
-      const Raw r0 = ld.load(u0);
-      const Raw r1 = ld.load(u1);
-      const Raw r2 = ld.load(u2);
-      const Raw r3 = ld.load(u3);
-      const Raw r4 = ld.load(u4);
-      const Raw r5 = ld.load(u5);
-      const Raw r6 = ld.load(u6);
-      const Raw r7 = ld.load(u7);
-      if (SRC) {
-        acc_add(acc, r0, deg_src[u0]); acc_add(acc, r1, deg_src[u1]);
-        acc_add(acc, r2, deg_src[u2]); acc_add(acc, r3, deg_src[u3]);
-        acc_add(acc, r4, deg_src[u4]); acc_add(acc, r5, deg_src[u5]);
-        acc_add(acc, r6, deg_src[u6]); acc_add(acc, r7, deg_src[u7]);
-      } else {
-        acc_add(acc, r0, 1.f); acc_add(acc, r1, 1.f);
-        acc_add(acc, r2, 1.f); acc_add(acc, r3, 1.f);
-        acc_add(acc, r4, 1.f); acc_add(acc, r5, 1.f);
-        acc_add(acc, r6, 1.f); acc_add(acc, r7, 1.f);
-      }
-    }
-  }
-  for (; e + 3 < e1; e += 4) {
-    const int u0 = colidx[e], u1 = colidx[e + 1];
-    const int u2 = colidx[e + 2], u3 = colidx[e + 3];
-    const Raw r0 = ld.load(u0);
-    const Raw r1 = ld.load(u1);
-    const Raw r2 = ld.load(u2);
-    const Raw r3 = ld.load(u3);
-    if (SRC) {
-      acc_add(acc, r0, deg_src[u0]); acc_add(acc, r1, deg_src[u1]);
-      acc_add(acc, r2, deg_src[u2]); acc_add(acc, r3, deg_src[u3]);
-    } else {
-      acc_add(acc, r0, 1.f); acc_add(acc, r1, 1.f);
-      acc_add(acc, r2, 1.f); acc_add(acc, r3, 1.f);
-    }
-  }
-  for (; e < e1; ++e) {
-    const int u0 = colidx[e];
-    const Raw r0 = ld.load(u0);
-    acc_add(acc, r0, SRC ? deg_src[u0] : 1.f);
-  }
+    float* __restrict__ acc, const LD& ld, const int* __restrict__ colidx,
+    const float* __restrict__ weight, int64_t e, int64_t e1) {
+  if constexpr (UN >= 16)
+    for (; e + 15 < e1; e += 16) accum_group<16, T, W>(acc, ld, colidx, weight, e);
+  if constexpr (UN >= 8)
+    for (; e + 7 < e1; e += 8) accum_group<8, T, W>(acc, ld, colidx, weight, e);
+  for (; e + 3 < e1; e += 4) accum_group<4, T, W>(acc, ld, colidx, weight, e);
+  for (; e < e1; ++e) accum_group<1, T, W>(acc, ld, colidx, weight, e);
 }
 
 // tail path: unit straddles the column window (only when its width is
 // not a multiple of EPU; engine pads dims to 8 so this is cold).
-// Scalar loads, dynamic-bound loops.
-template <typename T, int EPU>
+// Scalar loads, dynamic-bound loops. The per-source weight keeps a
+// run-time null check here (weight is null for Weight::kNone): resolving
+// it at compile time changes nothing on this path, but without it the
+// allocator packs the 8-deep no-weight kernels into 58 VGPRs / 8 waves
+// and serialises their unpack behind the last gather, which measured
+// 2-4% slower than 88 VGPRs / 5 waves (profiles/r37).
+template <typename T, Weight W>
 __device__ void row_accum_tail(
     float* __restrict__ acc, const T* __restrict__ x, int64_t ld, int64_t col0,
     int nvalid, const int* __restrict__ colidx,
-    const float* __restrict__ deg_src, int64_t e0, int64_t e1) {
+    const float* __restrict__ weight, int64_t e0, int64_t e1) {
   for (int64_t e = e0; e < e1; ++e) {
     const int u0 = colidx[e];
     const T* r = x + (int64_t)u0 * ld + col0;
-    const float w0 = deg_src ? deg_src[u0] : 1.f;
+    const float w0 =
+        W == Weight::kEdge ? weight[e] : (weight ? weight[u0] : 1.f);
     for (int j = 0; j < nvalid; ++j) acc[j] += w0 * elt_to_f32(r[j]);
   }
 }
@@ -207,27 +171,26 @@ __device__ void row_accum_tail(
 // launch covers (ld == col_end, col_base == 0 for a whole-matrix pass;
 // a column-phase pass sweeps a 64-col window of a wider matrix so the
 // fp32 partial buffer is touched once per much-wider source strip).
-template <typename T, typename OT, int TEAM, int UN, bool BUF, bool SRC>
+// `weight` is deg_src (indexed by source) or edge_val (indexed by edge)
+// as W says; unused for Weight::kNone.
+template <typename T, typename OT, int TEAM, int UN, bool BUF, Weight W>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(
     OT* __restrict__ out, const T* __restrict__ x,
     const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
-    const float* __restrict__ deg_dst, const float* __restrict__ deg_src,
+    const float* __restrict__ deg_dst, const float* __restrict__ weight,
     const int* __restrict__ row_order, int num_rows, int64_t ld,
     int64_t col_base, int64_t col_end, bool accumulate, unsigned x_bytes) {
   constexpr int EPU = EltTraits<T>::kPerVec;
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
+  const RowTeam<TEAM> rt;
 
   const int64_t col0 =
-      col_base + ((int64_t)blockIdx.y * TEAM + lane) * EPU;
+      col_base + ((int64_t)blockIdx.y * TEAM + rt.lane) * EPU;
   const bool full = (col0 + EPU) <= col_end;
   const int nvalid =
       full ? EPU : (col0 < col_end ? (int)(col_end - col0) : 0);
 
   if (full) {
-    for (int ri = team; ri < num_rows; ri += nteams) {
+    for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
       const int row = row_order ? row_order[ri] : ri;
       const int64_t e0 = rowptr[row];
       const int64_t e1 = rowptr[row + 1];
@@ -245,33 +208,27 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
             __builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, x_bytes,
                                               0x00020000),
             (unsigned)(ld * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-        row_accum_vec<T, EPU, UN, SRC>(acc, g, colidx, deg_src, e0, e1);
+        row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
       } else {
         GlobalGather<T> g{x, ld, col0};
-        row_accum_vec<T, EPU, UN, SRC>(acc, g, colidx, deg_src, e0, e1);
+        row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
       }
       if (deg_dst) {
         const float s = deg_dst[row];
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] *= s;
       }
-      if constexpr (std::is_same<OT, unsigned short>::value) {
-        store_bf16x8(o, acc);
-      } else if constexpr (EPU == 8) {
-        store_f32x8(o, acc);
-      } else {
-        store_f32x4(o, acc);
-      }
+      store_vec(o, acc);
     }
   } else if (nvalid > 0) {
-    for (int ri = team; ri < num_rows; ri += nteams) {
+    for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
       const int row = row_order ? row_order[ri] : ri;
       float acc[EPU];
       OT* o = out + (int64_t)row * ld + col0;
       for (int j = 0; j < nvalid; ++j)
         acc[j] = accumulate ? elt_to_f32(o[j]) : 0.f;
-      row_accum_tail<T, EPU>(acc, x, ld, col0, nvalid, colidx, deg_src,
-                             rowptr[row], rowptr[row + 1]);
+      row_accum_tail<T, W>(acc, x, ld, col0, nvalid, colidx, weight,
+                           rowptr[row], rowptr[row + 1]);
       const float s = deg_dst ? deg_dst[row] : 1.f;
       for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
     }
@@ -310,170 +267,77 @@ static const SpmmKnobs& spmm_knobs() {
   return g_spmm_knobs;
 }
 
-template <typename T, typename OT>
+// The one spmm_kernel launch: geometry from the column window, gather
+// engine from the matrix size, TEAM and BUF lifted to template constants.
+// team_override == 0 picks the team by width.
+template <typename T, typename OT, int UN, Weight W>
 void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
-                 const int* colidx, const float* deg_dst,
-                 const float* deg_src, const int* row_order, int num_rows,
-                 int64_t ld, int64_t col_base, int64_t col_end,
-                 bool accumulate, size_t x_elems, hipStream_t stream) {
+                 const int* colidx, const float* deg_dst, const float* weight,
+                 const int* row_order, int num_rows, int64_t ld,
+                 int64_t col_base, int64_t col_end, bool accumulate,
+                 size_t x_elems, int team_override, hipStream_t stream) {
   constexpr int EPU = EltTraits<T>::kPerVec;
-  const SpmmKnobs& kn = spmm_knobs();
-  const int64_t ncols = col_end - col_base;
-  const int64_t units = (ncols + EPU - 1) / EPU;
-  int team = 8;
-  while (team < units && team < 64) team *= 2;
-  if (kn.team_override) team = kn.team_override;
-  const int col_tiles = (int)((units + team - 1) / team);
-  const int tpb = kBlock / team;
-  dim3 grid(roc_grid_1d(num_rows, tpb, 8192), col_tiles);
-  const int un = kn.unroll;
+  const int64_t units = (col_end - col_base + EPU - 1) / EPU;
+  const int team = team_override ? team_override : row_team_size(units);
+  const dim3 grid =
+      row_team_grid(num_rows, team, (int)((units + team - 1) / team));
   const size_t xb = x_elems * sizeof(T);
-  const bool buf = xb < (size_t)UINT_MAX && kn.allow_buffer;
+  const bool buf = xb < (size_t)UINT_MAX && spmm_knobs().allow_buffer;
   const unsigned x_bytes = (unsigned)(buf ? xb : 0);
   // measured (scripts/bench_spmm.py, Reddit shape): degree-descending
   // scheduling wins for wide rows (D=256: -13%) but loses for narrow
   // ones (D=48: +10% — the indirection costs more than the skew tail)
   if (team < 16) row_order = nullptr;
-#define ROC_SPMM_L3(TEAM_, UN_, BUF_)                                       \
-  do {                                                                      \
-    if (deg_src) {                                                          \
-      hipLaunchKernelGGL((spmm_kernel<T, OT, TEAM_, UN_, BUF_, true>),     \
-                         grid,                                              \
-                         dim3(kBlock), 0, stream, out, x, rowptr, colidx,   \
-                         deg_dst, deg_src, row_order, num_rows, ld,         \
-                         col_base, col_end, accumulate, x_bytes);           \
-    } else {                                                                \
-      hipLaunchKernelGGL((spmm_kernel<T, OT, TEAM_, UN_, BUF_, false>),    \
-                         grid,                                              \
-                         dim3(kBlock), 0, stream, out, x, rowptr, colidx,   \
-                         deg_dst, deg_src, row_order, num_rows, ld,         \
-                         col_base, col_end, accumulate, x_bytes);           \
-    }                                                                       \
-  } while (0)
-#define ROC_SPMM_L2(TEAM_)                                                  \
-  do {                                                                      \
-    if (buf) {                                                              \
-      if (un >= 16) { ROC_SPMM_L3(TEAM_, 16, true); }                       \
-      else if (un >= 8) { ROC_SPMM_L3(TEAM_, 8, true); }                    \
-      else { ROC_SPMM_L3(TEAM_, 4, true); }                                 \
-    } else {                                                                \
-      if (un >= 16) { ROC_SPMM_L3(TEAM_, 16, false); }                      \
-      else if (un >= 8) { ROC_SPMM_L3(TEAM_, 8, false); }                   \
-      else { ROC_SPMM_L3(TEAM_, 4, false); }                                \
-    }                                                                       \
-  } while (0)
-  switch (team) {
-    case 8:  ROC_SPMM_L2(8);  break;
-    case 16: ROC_SPMM_L2(16); break;
-    case 32: ROC_SPMM_L2(32); break;
-    default: ROC_SPMM_L2(64);
-  }
-#undef ROC_SPMM_L2
-#undef ROC_SPMM_L3
+  dispatch_team(team, [&](auto team_c) {
+    dispatch_bool(buf, [&](auto buf_c) {
+      hipLaunchKernelGGL(
+          (spmm_kernel<T, OT, decltype(team_c)::value, UN,
+                       decltype(buf_c)::value, W>),
+          grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
+          weight, row_order, num_rows, ld, col_base, col_end, accumulate,
+          x_bytes);
+    });
+  });
 }
 
-// ---------------------------------------------------------------------------
-// Edge-weighted SpMM + its edge-value gradient (the edge-tensor ops).
-// out[v,:] (+)= deg_dst[v] * sum_{e in row v} edge_val[e] * x[col_e,:]
-// Same row-team geometry as spmm_kernel; weights are per-EDGE (not
-// per-source like deg_src), loaded sequentially -> one scalar broadcast
-// per gather. 4-deep unrolled; capability path, not the fused-GCN hot
-// path, so one unroll depth is enough.
-// ---------------------------------------------------------------------------
-
-// per-row accumulate loop shared by both gather engines (8 gathers in
-// flight via 2x 4-group issue; per-edge scalar weight broadcast)
-template <typename T, int EPU, typename LD>
-__device__ __forceinline__ void edge_accum_row(
-    float* __restrict__ acc, const LD& ld, const int* __restrict__ colidx,
-    const float* __restrict__ edge_val, int64_t e, int64_t e1) {
-  using Raw = typename RawVec<T>::type;
-  for (; e + 3 < e1; e += 4) {
-    const int u0 = colidx[e], u1 = colidx[e + 1];
-    const int u2 = colidx[e + 2], u3 = colidx[e + 3];
-    const float w0 = edge_val[e], w1 = edge_val[e + 1];
-    const float w2 = edge_val[e + 2], w3 = edge_val[e + 3];
-    const Raw r0 = ld.load(u0), r1 = ld.load(u1);
-    const Raw r2 = ld.load(u2), r3 = ld.load(u3);
-    acc_add(acc, r0, w0); acc_add(acc, r1, w1);
-    acc_add(acc, r2, w2); acc_add(acc, r3, w3);
-  }
-  for (; e < e1; ++e) {
-    const Raw r0 = ld.load(colidx[e]);
-    acc_add(acc, r0, edge_val[e]);
-  }
-}
-
-template <typename T, int TEAM, bool BUF>
-__global__ __launch_bounds__(kBlock) void spmm_edge_kernel(
-    T* __restrict__ out, const T* __restrict__ x,
-    const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
-    const float* __restrict__ edge_val, const float* __restrict__ deg_dst,
-    const int* __restrict__ row_order, int num_rows, int64_t D,
-    bool accumulate, unsigned x_bytes) {
-  constexpr int EPU = EltTraits<T>::kPerVec;
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
-  const int64_t col0 = ((int64_t)blockIdx.y * TEAM + lane) * EPU;
-  const bool full = (col0 + EPU) <= D;
-  const int nvalid = full ? EPU : (col0 < D ? (int)(D - col0) : 0);
-
-  if (full) {
-    for (int ri = team; ri < num_rows; ri += nteams) {
-      const int row = row_order ? row_order[ri] : ri;
-      const int64_t e0 = rowptr[row];
-      const int64_t e1 = rowptr[row + 1];
-      float acc[EPU];
-      T* o = out + (int64_t)row * D + col0;
-      if (accumulate) {
-#pragma unroll
-        for (int j = 0; j < EPU; ++j) acc[j] = elt_to_f32(o[j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < EPU; ++j) acc[j] = 0.f;
-      }
-      if constexpr (BUF) {
-        BufferGather<T> ld{
-            __builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, x_bytes,
-                                              0x00020000),
-            (unsigned)(D * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-        edge_accum_row<T, EPU>(acc, ld, colidx, edge_val, e0, e1);
-      } else {
-        GlobalGather<T> ld{x, D, col0};
-        edge_accum_row<T, EPU>(acc, ld, colidx, edge_val, e0, e1);
-      }
-      if (deg_dst) {
-        const float s = deg_dst[row];
-#pragma unroll
-        for (int j = 0; j < EPU; ++j) acc[j] *= s;
-      }
-      if constexpr (EPU == 8) store_bf16x8(o, acc); else store_f32x4(o, acc);
-    }
-  } else if (nvalid > 0) {
-    for (int ri = team; ri < num_rows; ri += nteams) {
-      const int row = row_order ? row_order[ri] : ri;
-      float acc[EPU];
-      T* o = out + (int64_t)row * D + col0;
-      for (int j = 0; j < nvalid; ++j)
-        acc[j] = accumulate ? elt_to_f32(o[j]) : 0.f;
-      for (int64_t e = rowptr[row]; e < rowptr[row + 1]; ++e) {
-        const T* r = x + (int64_t)colidx[e] * D + col0;
-        const float w0 = edge_val[e];
-        for (int j = 0; j < nvalid; ++j) acc[j] += w0 * elt_to_f32(r[j]);
-      }
-      const float s = deg_dst ? deg_dst[row] : 1.f;
-      for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
-    }
-  }
-}
-
-// dw[e] = <dy[row_e,:], x[col_e,:]>  (fp32 accumulate).
+// dw[e] = <dy[row_e,:], x[col_e,:]>  (fp32 accumulate) — the edge-value
+// gradient of the per-edge-weighted SpMM.
 // Team per row; per edge each lane dots its strided D-chunks, then a
-// log2(TEAM) shfl_xor tree folds the team partials; lane 0 stores.
-// Teams are contiguous, power-of-2-aligned lane groups, so the xor
-// tree never crosses a team boundary within the wave64 front.
+// team_reduce_sum folds the team partials; lane 0 stores.
+template <typename T, int EPU>
+__device__ __forceinline__ float dot_unit(
+    const float (&a)[EPU], const typename RawVec<T>::type& r) {
+  float b[EPU];
+#pragma unroll
+  for (int j = 0; j < EPU; ++j) b[j] = 0.f;
+  acc_add(b, r, 1.f);
+  float p = 0.f;
+#pragma unroll
+  for (int j = 0; j < EPU; ++j) p += a[j] * b[j];
+  return p;
+}
+
+// N edges of the fast path: gathers queued N deep, N team folds, N stores
+template <int N, typename T, int TEAM, int EPU>
+__device__ __forceinline__ void edge_dot_group(
+    float* __restrict__ dw, const float (&a)[EPU], const GlobalGather<T>& g,
+    const int* __restrict__ colidx, int64_t e, bool live, int lane) {
+  float p[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = 0.f;
+  if (live)
+    gather_group<N, T>(g, colidx, e,
+                       [&](int i, int, const typename RawVec<T>::type& r) {
+      p[i] = dot_unit<T>(a, r);
+    });
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = team_reduce_sum<TEAM>(p[i]);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) dw[e + i] = p[i];
+  }
+}
+
 template <typename T, int TEAM>
 __global__ __launch_bounds__(kBlock) void edge_dot_kernel(
     float* __restrict__ dw, const T* __restrict__ dy,
@@ -481,90 +345,29 @@ __global__ __launch_bounds__(kBlock) void edge_dot_kernel(
     const int* __restrict__ colidx, int num_rows, int64_t D) {
   constexpr int EPU = EltTraits<T>::kPerVec;
   using Raw = typename RawVec<T>::type;
-  const int tpb = kBlock / TEAM;
-  const int team = blockIdx.x * tpb + (int)threadIdx.x / TEAM;
-  const int lane = (int)threadIdx.x % TEAM;
-  const int nteams = gridDim.x * tpb;
+  const RowTeam<TEAM> rt;
+  const int lane = rt.lane;
   // fast path: one chunk covers D (TEAM*EPU >= D, e.g. TEAM=8 D<=64
   // bf16). The dy row chunk is loaded ONCE per row (hoisted out of the
   // edge loop) and x gathers are queued 4 deep — the naive per-edge
   // load/reduce version was 4x off the gather-service rate (r2c16).
   if ((int64_t)TEAM * EPU >= D && D % EPU == 0) {
-    const int cvalid = (int)(D / EPU);  // lanes with a live chunk
-    for (int row = team; row < num_rows; row += nteams) {
+    const bool live = lane < (int)(D / EPU);  // lane has a chunk
+    const GlobalGather<T> g{x, D, (int64_t)lane * EPU};
+    for (int row = rt.team; row < num_rows; row += rt.nteams) {
       const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
-      const T* dyr = dy + (int64_t)row * D;
       float a[EPU] = {0.f};
-      if (lane < cvalid) {
-        const Raw ra = load_raw(dyr + (int64_t)lane * EPU);
-        acc_add(a, ra, 1.f);
-      }
+      if (live) acc_add(a, load_raw(dy + (int64_t)row * D + g.col0), 1.f);
       int64_t e = e0;
-      for (; e + 3 < e1; e += 4) {
-        const int u0 = colidx[e], u1 = colidx[e + 1];
-        const int u2 = colidx[e + 2], u3 = colidx[e + 3];
-        float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-        if (lane < cvalid) {
-          const int64_t c = (int64_t)lane * EPU;
-          const Raw r0 = load_raw(x + (int64_t)u0 * D + c);
-          const Raw r1 = load_raw(x + (int64_t)u1 * D + c);
-          const Raw r2 = load_raw(x + (int64_t)u2 * D + c);
-          const Raw r3 = load_raw(x + (int64_t)u3 * D + c);
-          float b[EPU];
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) b[j] = 0.f;
-          acc_add(b, r0, 1.f);
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) p0 += a[j] * b[j];
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) b[j] = 0.f;
-          acc_add(b, r1, 1.f);
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) p1 += a[j] * b[j];
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) b[j] = 0.f;
-          acc_add(b, r2, 1.f);
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) p2 += a[j] * b[j];
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) b[j] = 0.f;
-          acc_add(b, r3, 1.f);
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) p3 += a[j] * b[j];
-        }
-#pragma unroll
-        for (int off = TEAM / 2; off > 0; off >>= 1) {
-          p0 += __shfl_xor(p0, off, 64);
-          p1 += __shfl_xor(p1, off, 64);
-          p2 += __shfl_xor(p2, off, 64);
-          p3 += __shfl_xor(p3, off, 64);
-        }
-        if (lane == 0) {
-          dw[e] = p0; dw[e + 1] = p1; dw[e + 2] = p2; dw[e + 3] = p3;
-        }
-      }
-      for (; e < e1; ++e) {
-        float p = 0.f;
-        if (lane < cvalid) {
-          const Raw rb = load_raw(x + (int64_t)colidx[e] * D
-                                  + (int64_t)lane * EPU);
-          float b[EPU];
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) b[j] = 0.f;
-          acc_add(b, rb, 1.f);
-#pragma unroll
-          for (int j = 0; j < EPU; ++j) p += a[j] * b[j];
-        }
-#pragma unroll
-        for (int off = TEAM / 2; off > 0; off >>= 1)
-          p += __shfl_xor(p, off, 64);
-        if (lane == 0) dw[e] = p;
-      }
+      for (; e + 3 < e1; e += 4)
+        edge_dot_group<4, T, TEAM>(dw, a, g, colidx, e, live, lane);
+      for (; e < e1; ++e)
+        edge_dot_group<1, T, TEAM>(dw, a, g, colidx, e, live, lane);
     }
     return;
   }
   // general path (wide D): chunk loop per edge
-  for (int row = team; row < num_rows; row += nteams) {
+  for (int row = rt.team; row < num_rows; row += rt.nteams) {
     const int64_t e0 = rowptr[row], e1 = rowptr[row + 1];
     const T* dyr = dy + (int64_t)row * D;
     for (int64_t e = e0; e < e1; ++e) {
@@ -583,48 +386,10 @@ __global__ __launch_bounds__(kBlock) void edge_dot_kernel(
       // scalar tail, lane-strided, for D % EPU != 0 (cold; dims padded)
       for (int64_t j = (D / EPU) * EPU + lane; j < D; j += TEAM)
         p += elt_to_f32(dyr[j]) * elt_to_f32(xr[j]);
-#pragma unroll
-      for (int off = TEAM / 2; off > 0; off >>= 1)
-        p += __shfl_xor(p, off, 64);
+      p = team_reduce_sum<TEAM>(p);
       if (lane == 0) dw[e] = p;
     }
   }
-}
-
-template <typename T>
-void launch_spmm_edge(T* out, const T* x, const int64_t* rowptr,
-                      const int* colidx, const float* edge_val,
-                      const float* deg_dst, const int* row_order,
-                      int num_rows, int64_t D, bool accumulate,
-                      size_t x_elems, hipStream_t stream) {
-  constexpr int EPU = EltTraits<T>::kPerVec;
-  const int64_t units = (D + EPU - 1) / EPU;
-  int team = 8;
-  while (team < units && team < 64) team *= 2;
-  const int col_tiles = (int)((units + team - 1) / team);
-  const int tpb = kBlock / team;
-  dim3 grid(roc_grid_1d(num_rows, tpb, 8192), col_tiles);
-  const size_t xb = x_elems * sizeof(T);
-  const bool buf = xb < (size_t)UINT_MAX && spmm_knobs().allow_buffer;
-  if (team < 16) row_order = nullptr;
-#define ROC_SPMME_L(TEAM_, BUF_)                                            \
-  hipLaunchKernelGGL((spmm_edge_kernel<T, TEAM_, BUF_>), grid, dim3(kBlock),\
-                     0, stream, out, x, rowptr, colidx, edge_val, deg_dst,  \
-                     row_order, num_rows, D, accumulate,                    \
-                     (unsigned)(buf ? xb : 0))
-#define ROC_SPMME_T(TEAM_)                                                  \
-  do {                                                                      \
-    if (buf) { ROC_SPMME_L(TEAM_, true); }                                  \
-    else { ROC_SPMME_L(TEAM_, false); }                                     \
-  } while (0)
-  switch (team) {
-    case 8:  ROC_SPMME_T(8);  break;
-    case 16: ROC_SPMME_T(16); break;
-    case 32: ROC_SPMME_T(32); break;
-    default: ROC_SPMME_T(64);
-  }
-#undef ROC_SPMME_T
-#undef ROC_SPMME_L
 }
 
 template <typename T>
@@ -632,21 +397,26 @@ void launch_edge_dot(float* dw, const T* dy, const T* x,
                      const int64_t* rowptr, const int* colidx, int num_rows,
                      int64_t D, hipStream_t stream) {
   constexpr int EPU = EltTraits<T>::kPerVec;
-  const int64_t units = (D + EPU - 1) / EPU;
-  int team = 8;
-  while (team < units && team < 64) team *= 2;
-  const int tpb = kBlock / team;
-  dim3 grid(roc_grid_1d(num_rows, tpb, 8192));
-#define ROC_EDOT_L(TEAM_)                                                   \
-  hipLaunchKernelGGL((edge_dot_kernel<T, TEAM_>), grid, dim3(kBlock), 0,    \
-                     stream, dw, dy, x, rowptr, colidx, num_rows, D)
-  switch (team) {
-    case 8:  ROC_EDOT_L(8);  break;
-    case 16: ROC_EDOT_L(16); break;
-    case 32: ROC_EDOT_L(32); break;
-    default: ROC_EDOT_L(64);
-  }
-#undef ROC_EDOT_L
+  const int team = row_team_size((D + EPU - 1) / EPU);
+  dispatch_team(team, [&](auto team_c) {
+    hipLaunchKernelGGL((edge_dot_kernel<T, decltype(team_c)::value>),
+                       row_team_grid(num_rows, team), dim3(kBlock), 0, stream,
+                       dw, dy, x, rowptr, colidx, num_rows, D);
+  });
+}
+
+void check_csr(const torch::Tensor& rowptr, const torch::Tensor& colidx,
+               int num_rows) {
+  ROC_CHECK_DEV_CONT(rowptr);
+  ROC_CHECK_DEV_CONT(colidx);
+  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr must be int64");
+  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, "colidx must be int32");
+  TORCH_CHECK(rowptr.size(0) == num_rows + 1, "rowptr size mismatch");
+}
+
+template <typename T>
+const T* opt_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 
 }  // namespace
@@ -662,10 +432,6 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           int64_t col_base, int64_t ncols) {
   ROC_CHECK_DEV_CONT(out);
   ROC_CHECK_DEV_CONT(x);
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr must be int64");
-  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, "colidx must be int32");
   TORCH_CHECK(out.scalar_type() == x.scalar_type() ||
                   (out.scalar_type() == torch::kFloat32 &&
                    x.scalar_type() == torch::kBFloat16),
@@ -673,54 +439,53 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
   const int num_rows = (int)out.size(0);
   const int64_t D = out.size(1);
   TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  TORCH_CHECK(rowptr.size(0) == num_rows + 1, "rowptr size mismatch");
+  check_csr(rowptr, colidx, num_rows);
   // column-phase pass: touch only [col_base, col_base+ncols) of every
   // row (ncols == 0 -> the whole row). The stride stays D.
   const int64_t col_end = ncols > 0 ? col_base + ncols : D;
   TORCH_CHECK(col_base >= 0 && col_base < col_end && col_end <= D,
               "bad column window");
-  const float* dd =
-      deg_dst.has_value() ? deg_dst->data_ptr<float>() : nullptr;
-  const float* ds =
-      deg_src.has_value() ? deg_src->data_ptr<float>() : nullptr;
-  const int* ro =
-      row_order.has_value() ? row_order->data_ptr<int>() : nullptr;
+  const float* ds = opt_ptr<float>(deg_src);
+  const SpmmKnobs& kn = spmm_knobs();
   auto stream = roc_stream();
-  if (x.scalar_type() == torch::kBFloat16 &&
-      out.scalar_type() == torch::kBFloat16) {
-    launch_spmm<unsigned short, unsigned short>(
-        (unsigned short*)out.data_ptr(), (const unsigned short*)x.data_ptr(),
-        rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), dd, ds, ro,
-        num_rows, D, col_base, col_end, accumulate, (size_t)x.numel(),
-        stream);
-  } else if (x.scalar_type() == torch::kBFloat16) {
-    launch_spmm<unsigned short, float>(
-        out.data_ptr<float>(), (const unsigned short*)x.data_ptr(),
-        rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), dd, ds, ro,
-        num_rows, D, col_base, col_end, accumulate, (size_t)x.numel(),
-        stream);
-  } else if (x.scalar_type() == torch::kFloat32) {
-    launch_spmm<float, float>(out.data_ptr<float>(), x.data_ptr<float>(),
-                       rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), dd,
-                       ds, ro, num_rows, D, col_base, col_end, accumulate,
-                       (size_t)x.numel(), stream);
-  } else {
-    TORCH_CHECK(false, "spmm: unsupported dtype (bf16/f32 only)");
-  }
+  dispatch_elt(x.scalar_type(), "spmm", [&](auto xt) {
+    dispatch_elt(out.scalar_type(), "spmm", [&](auto ot) {
+      using T = typename decltype(xt)::type;
+      using OT = typename decltype(ot)::type;
+      // (fp32 x with bf16 out is rejected above and never instantiated)
+      if constexpr (sizeof(OT) >= sizeof(T)) {
+        auto go = [&](auto un_c, auto w_c) {
+          launch_spmm<T, OT, decltype(un_c)::value, decltype(w_c)::value>(
+              (OT*)out.data_ptr(), (const T*)x.data_ptr(),
+              rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
+              opt_ptr<float>(deg_dst), ds, opt_ptr<int>(row_order), num_rows,
+              D, col_base, col_end, accumulate, (size_t)x.numel(),
+              kn.team_override, stream);
+        };
+        auto by_weight = [&](auto un_c) {
+          if (ds) go(un_c, std::integral_constant<Weight, Weight::kSrc>{});
+          else go(un_c, std::integral_constant<Weight, Weight::kNone>{});
+        };
+        if (kn.unroll >= 16) by_weight(std::integral_constant<int, 16>{});
+        else if (kn.unroll >= 8) by_weight(std::integral_constant<int, 8>{});
+        else by_weight(std::integral_constant<int, 4>{});
+      }
+    });
+  });
   ROC_HIP_CHECK(hipGetLastError());
 }
 
+// Per-edge-weighted SpMM (the edge-tensor op):
+// out[v,:] (+)= deg_dst[v] * sum_{e in row v} edge_val[e] * x[col_e,:]
+// Capability path, not the fused-GCN hot path, so one unroll depth (4),
+// OT == T and the whole-matrix window are all it instantiates.
 void spmm_edge(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
                torch::Tensor colidx, torch::Tensor edge_val,
                c10::optional<torch::Tensor> deg_dst,
                c10::optional<torch::Tensor> row_order, bool accumulate) {
   ROC_CHECK_DEV_CONT(out);
   ROC_CHECK_DEV_CONT(x);
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
   ROC_CHECK_DEV_CONT(edge_val);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr must be int64");
-  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, "colidx must be int32");
   TORCH_CHECK(edge_val.scalar_type() == torch::kFloat32,
               "edge_val must be fp32");
   TORCH_CHECK(edge_val.numel() == colidx.numel(), "edge_val size mismatch");
@@ -728,27 +493,17 @@ void spmm_edge(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
   const int num_rows = (int)out.size(0);
   const int64_t D = out.size(1);
   TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  TORCH_CHECK(rowptr.size(0) == num_rows + 1, "rowptr size mismatch");
-  const float* dd =
-      deg_dst.has_value() ? deg_dst->data_ptr<float>() : nullptr;
-  const int* ro =
-      row_order.has_value() ? row_order->data_ptr<int>() : nullptr;
+  check_csr(rowptr, colidx, num_rows);
   auto stream = roc_stream();
-  if (x.scalar_type() == torch::kBFloat16) {
-    launch_spmm_edge<unsigned short>(
-        (unsigned short*)out.data_ptr(), (const unsigned short*)x.data_ptr(),
+  dispatch_elt(x.scalar_type(), "spmm_edge", [&](auto xt) {
+    using T = typename decltype(xt)::type;
+    launch_spmm<T, T, 4, Weight::kEdge>(
+        (T*)out.data_ptr(), (const T*)x.data_ptr(),
         rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
-        edge_val.data_ptr<float>(), dd, ro, num_rows, D, accumulate,
-        (size_t)x.numel(), stream);
-  } else if (x.scalar_type() == torch::kFloat32) {
-    launch_spmm_edge<float>(
-        out.data_ptr<float>(), x.data_ptr<float>(),
-        rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
-        edge_val.data_ptr<float>(), dd, ro, num_rows, D, accumulate,
-        (size_t)x.numel(), stream);
-  } else {
-    TORCH_CHECK(false, "spmm_edge: unsupported dtype (bf16/f32 only)");
-  }
+        opt_ptr<float>(deg_dst), edge_val.data_ptr<float>(),
+        opt_ptr<int>(row_order), num_rows, D, 0, D, accumulate,
+        (size_t)x.numel(), 0, stream);
+  });
   ROC_HIP_CHECK(hipGetLastError());
 }
 
@@ -757,28 +512,19 @@ void edge_dot(torch::Tensor dw, torch::Tensor dy, torch::Tensor x,
   ROC_CHECK_DEV_CONT(dw);
   ROC_CHECK_DEV_CONT(dy);
   ROC_CHECK_DEV_CONT(x);
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
   TORCH_CHECK(dw.scalar_type() == torch::kFloat32, "dw must be fp32");
   TORCH_CHECK(dw.numel() == colidx.numel(), "dw size mismatch");
   TORCH_CHECK(dy.scalar_type() == x.scalar_type(), "dtype mismatch");
   const int num_rows = (int)dy.size(0);
   const int64_t D = dy.size(1);
   TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  TORCH_CHECK(rowptr.size(0) == num_rows + 1, "rowptr size mismatch");
+  check_csr(rowptr, colidx, num_rows);
   auto stream = roc_stream();
-  if (dy.scalar_type() == torch::kBFloat16) {
-    launch_edge_dot<unsigned short>(
-        dw.data_ptr<float>(), (const unsigned short*)dy.data_ptr(),
-        (const unsigned short*)x.data_ptr(), rowptr.data_ptr<int64_t>(),
-        colidx.data_ptr<int>(), num_rows, D, stream);
-  } else if (dy.scalar_type() == torch::kFloat32) {
-    launch_edge_dot<float>(
-        dw.data_ptr<float>(), dy.data_ptr<float>(), x.data_ptr<float>(),
-        rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), num_rows, D,
-        stream);
-  } else {
-    TORCH_CHECK(false, "edge_dot: unsupported dtype (bf16/f32 only)");
-  }
+  dispatch_elt(dy.scalar_type(), "edge_dot", [&](auto xt) {
+    using T = typename decltype(xt)::type;
+    launch_edge_dot<T>(dw.data_ptr<float>(), (const T*)dy.data_ptr(),
+                       (const T*)x.data_ptr(), rowptr.data_ptr<int64_t>(),
+                       colidx.data_ptr<int>(), num_rows, D, stream);
+  });
   ROC_HIP_CHECK(hipGetLastError());
 }

@@ -30,8 +30,9 @@ def has_ext() -> bool:
 _PHASE_COLS: Optional[int] = None
 
 # -- async dW: the weight-grad GEMMs are independent of the big SpMM^T
-# that follows them in backward, and gemm_atb ACCUMULATES (fp32
-# atomics), so when the param's .grad buffer exists (flat-grad setup)
+# that follows them in backward, and gemm_atb ACCUMULATES (C += the
+# split-K partials, folded in a fixed order, all on the launching
+# stream), so when the param's .grad buffer exists (flat-grad setup)
 # the dW launches on a side stream and lands directly in .grad while
 # the aggregation backward runs. dw_flush() joins the side stream
 # before any gradient consumer (all-reduce / Adam).
@@ -107,6 +108,35 @@ def _hip(x: torch.Tensor) -> bool:
 # ScatterGather (CSR SpMM neighbor aggregation) — the hot op
 # ---------------------------------------------------------------------------
 
+def _strip_spmm(x, strips, num_rows, row_scale):
+    """Source-strip-blocked SpMM: each pass gathers from an L2-resident
+    source window; partials accumulate in fp32 (one rounding total —
+    same numerics as single-pass). Wide feature dims additionally sweep
+    column PHASES: a 64-col phase over 4x-wider strips keeps the same
+    gather working set (rows x cols bytes) while the fp32 partial buffer
+    is re-read/re-written 4x less often — partial traffic, not gathers,
+    was the next bound (profiles/r23). The epilogue casts back to
+    x.dtype and applies the optional fp32 row_scale."""
+    D = x.shape[1]
+    out32 = torch.empty(num_rows, D, dtype=torch.float32, device=x.device)
+    ph = _phase_cols()
+    if ph and D % ph == 0 and D // ph >= 2:
+        phases = [(p, ph) for p in range(0, D, ph)]
+    else:
+        phases = [(0, 0)]  # one whole-row phase
+    for col_base, ncols in phases:
+        for i, (srp, sci) in enumerate(strips):
+            _C.spmm(out32, x, srp, sci, None, None, None, i > 0,
+                    col_base, ncols)
+    if x.dtype == torch.bfloat16 and D % 8 == 0:
+        out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
+        _C.cast_rowscale(out, out32, row_scale)  # fused epilogue
+        return out
+    if row_scale is not None:
+        out32 = out32 * row_scale.unsqueeze(1)
+    return out32.to(x.dtype)
+
+
 class _SpMM(torch.autograd.Function):
     """out[v] = sum over in-neighbors of x[u] on a (possibly halo-extended,
     possibly degree-normalized) local CSR. Backward runs the same kernel on
@@ -120,34 +150,7 @@ class _SpMM(torch.autograd.Function):
         ctx.num_ext = num_ext
         ctx.bwd_strips = bwd_strips
         if _hip(x) and fwd_strips is not None and deg_src is None:
-            # source-strip-blocked schedule: each pass gathers from an
-            # L2-resident source window; partials accumulate in fp32
-            # (one rounding total — same numerics as single-pass).
-            # Wide feature dims additionally sweep column PHASES: a
-            # 64-col phase over 4x-wider strips keeps the same gather
-            # working set (rows x cols bytes) while the fp32 partial
-            # buffer is re-read/re-written 4x less often — partial
-            # traffic, not gathers, was the next bound (profiles/r23).
-            out32 = torch.empty(num_rows, x.shape[1], dtype=torch.float32,
-                                device=x.device)
-            D = x.shape[1]
-            ph = _phase_cols()
-            if ph and D % ph == 0 and D // ph >= 2:
-                for p in range(0, D, ph):
-                    for i, (srp, sci) in enumerate(fwd_strips):
-                        _C.spmm(out32, x, srp, sci, None, None, None,
-                                i > 0, p, ph)
-            else:
-                for i, (srp, sci) in enumerate(fwd_strips):
-                    _C.spmm(out32, x, srp, sci, None, None, None, i > 0)
-            if x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0:
-                out = torch.empty(num_rows, x.shape[1],
-                                  dtype=torch.bfloat16, device=x.device)
-                _C.cast_rowscale(out, out32, deg_dst)  # fused epilogue
-            else:
-                if deg_dst is not None:
-                    out32 = out32 * deg_dst.unsqueeze(1)
-                out = out32.to(x.dtype)
+            out = _strip_spmm(x, fwd_strips, num_rows, deg_dst)
         elif _hip(x):
             out = torch.empty(num_rows, x.shape[1], dtype=x.dtype, device=x.device)
             _C.spmm(out, x, rowptr, colidx, deg_dst, deg_src, row_order)
@@ -173,27 +176,11 @@ class _SpMM(torch.autograd.Function):
                 _C.rowscale(tmp, dy, deg_dst)
                 dy = tmp
             if ctx.bwd_strips is not None and deg_src is None:
-                dx32 = torch.empty(ctx.num_ext, dy.shape[1],
-                                   dtype=torch.float32, device=dy.device)
-                D = dy.shape[1]
-                ph = _phase_cols()
-                if ph and D % ph == 0 and D // ph >= 2:
-                    for p in range(0, D, ph):
-                        for i, (srp, sci) in enumerate(ctx.bwd_strips):
-                            _C.spmm(dx32, dy, srp, sci, None, None, None,
-                                    i > 0, p, ph)
-                else:
-                    for i, (srp, sci) in enumerate(ctx.bwd_strips):
-                        _C.spmm(dx32, dy, srp, sci, None, None, None, i > 0)
-                if dy.dtype == torch.bfloat16 and dy.shape[1] % 8 == 0:
-                    dx = torch.empty(ctx.num_ext, dy.shape[1],
-                                     dtype=torch.bfloat16,
-                                     device=dy.device)
-                    _C.cast_rowscale(dx, dx32, None)
-                    return (dx,) + (None,) * 12
-                return (dx32.to(dy.dtype),) + (None,) * 12
-            dx = torch.empty(ctx.num_ext, dy.shape[1], dtype=dy.dtype, device=dy.device)
-            _C.spmm(dx, dy, t_rowptr, t_colidx, deg_src, None, t_row_order)
+                dx = _strip_spmm(dy, ctx.bwd_strips, ctx.num_ext, None)
+            else:
+                dx = torch.empty(ctx.num_ext, dy.shape[1], dtype=dy.dtype,
+                                 device=dy.device)
+                _C.spmm(dx, dy, t_rowptr, t_colidx, deg_src, None, t_row_order)
         else:
             yin = dy
             if deg_dst is not None:
@@ -504,7 +491,7 @@ class _Linear(torch.autograd.Function):
             if (gbuf is not None and gbuf.dtype == torch.float32
                     and gbuf.is_contiguous() and gbuf.is_cuda):
                 # accumulate straight into .grad on the side stream
-                # (gemm_atb is += via fp32 atomics); return None so
+                # (gemm_atb is C += ordered split-K sum); return None so
                 # autograd does not accumulate a second copy
                 from .. import streamcheck
                 s = _dw_stream()

@@ -653,3 +653,206 @@ def test_spmm_schedule_equivalence():
     order = torch.argsort(-deg).int().to(DEV)
     _C.spmm(out_deg, x, rowptr, colidx, rsq, None, order)
     assert torch.equal(out_nat, out_deg)
+
+
+# ---------------------------------------------------------------------------
+# Row-team kernel family on one tiny explicit CSR: 64 destination rows,
+# row v has degree v (an empty row and every remainder of the 16/8/4/1
+# gather ladder), sources drawn from 200 rows.
+# ---------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def ladder_csr():
+    deg = torch.arange(64, dtype=torch.int64)
+    rowptr = torch.zeros(65, dtype=torch.int64)
+    rowptr[1:] = torch.cumsum(deg, 0)
+    gen = torch.Generator().manual_seed(37)
+    colidx = torch.randint(0, 200, (int(rowptr[-1]),), generator=gen,
+                           dtype=torch.int32)
+    assert colidx.numel() == 2016
+    return rowptr, colidx
+
+
+_SPMM_KNOBS = ("ROC_SPMM_UNROLL", "ROC_SPMM_BUFFER", "ROC_SPMM_TEAM")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("D", [64, 200])
+def test_spmm_knob_variants_bit_identical(ladder_csr, dtype, D):
+    """Unroll depth, gather engine and team size only regroup the same
+    in-edge-order sums: every variant equals the default bit for bit."""
+    import os
+    rowptr, colidx = (t.to(DEV) for t in ladder_csr)
+    torch.manual_seed(41)
+    x = torch.randn(200, D).to(dtype).to(DEV)
+    deg_src = (torch.rand(200) + 0.5).to(DEV)
+    saved = {k: os.environ.pop(k, None) for k in _SPMM_KNOBS}
+
+    def run(ds):
+        _ext().spmm_refresh_knobs()
+        out = torch.empty(64, D, dtype=dtype, device=DEV)
+        _ext().spmm(out, x, rowptr, colidx, None, ds, None)
+        return out
+
+    try:
+        want = {False: run(None), True: run(deg_src)}
+        assert want[False].float().abs().sum().item() > 0
+        for un in ("4", "8", "16"):
+            for buf in ("0", "1"):
+                for team in (None, "64"):
+                    os.environ["ROC_SPMM_UNROLL"] = un
+                    os.environ["ROC_SPMM_BUFFER"] = buf
+                    if team is None:
+                        os.environ.pop("ROC_SPMM_TEAM", None)
+                    else:
+                        os.environ["ROC_SPMM_TEAM"] = team
+                    for src in (False, True):
+                        got = run(deg_src if src else None)
+                        assert torch.equal(got, want[src]), \
+                            (un, buf, team, src)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        _ext().spmm_refresh_knobs()
+
+
+# D=8: one live unit in a team of 8; 41: scalar tail; 520 bf16 / 260 fp32:
+# 65 units -> a second column tile, and edge_dot's general path
+_EDGE_SHAPES = [(torch.bfloat16, 8), (torch.bfloat16, 41),
+                (torch.bfloat16, 64), (torch.bfloat16, 520),
+                (torch.float32, 8), (torch.float32, 41),
+                (torch.float32, 64), (torch.float32, 260)]
+
+
+@pytest.mark.parametrize("dtype,D", _EDGE_SHAPES)
+def test_spmm_edge_shapes(ladder_csr, dtype, D):
+    rowptr, colidx = ladder_csr
+    torch.manual_seed(43)
+    x = torch.randn(200, D).to(dtype)
+    w = torch.rand(colidx.numel())
+    deg = (rowptr[1:] - rowptr[:-1]).float()
+    dst = deg.clamp(min=1).rsqrt()
+    plain = ref.spmm_weighted(x.float(), rowptr, colidx, w, 64)
+    scaled = plain * dst.unsqueeze(1)
+    rp, ci, xd, wd, dd = (t.to(DEV) for t in (rowptr, colidx, x, w, dst))
+    order = torch.argsort(-deg).int().to(DEV)
+
+    def tol(want):
+        return 1e-4 if dtype == torch.float32 else \
+            want.abs().max().item() * 2 ** -7 + 1e-2
+
+    got = torch.empty(64, D, dtype=dtype, device=DEV)
+    _ext().spmm_edge(got, xd, rp, ci, wd, None, None, False)
+    assert torch.allclose(got.float().cpu(), plain, atol=tol(plain),
+                          rtol=0.05), (got.float().cpu() - plain).abs().max()
+    got = torch.empty(64, D, dtype=dtype, device=DEV)
+    _ext().spmm_edge(got, xd, rp, ci, wd, dd, order, False)
+    assert torch.allclose(got.float().cpu(), scaled, atol=tol(scaled),
+                          rtol=0.05), (got.float().cpu() - scaled).abs().max()
+    # two halves, split at each row's midpoint, second pass accumulates
+    mid = rowptr[:-1] + (rowptr[1:] - rowptr[:-1]) // 2
+    rp1 = torch.zeros(65, dtype=torch.int64)
+    rp1[1:] = torch.cumsum(mid - rowptr[:-1], 0)
+    rp2 = torch.zeros(65, dtype=torch.int64)
+    rp2[1:] = torch.cumsum(rowptr[1:] - mid, 0)
+    lo, md, hi = rowptr[:-1].tolist(), mid.tolist(), rowptr[1:].tolist()
+    e1 = torch.cat([torch.arange(lo[v], md[v]) for v in range(64)])
+    e2 = torch.cat([torch.arange(md[v], hi[v]) for v in range(64)])
+    got = torch.empty(64, D, dtype=dtype, device=DEV)
+    _ext().spmm_edge(got, xd, rp1.to(DEV), colidx[e1].to(DEV),
+                     w[e1].to(DEV), None, None, False)
+    _ext().spmm_edge(got, xd, rp2.to(DEV), colidx[e2].to(DEV),
+                     w[e2].to(DEV), dd, None, True)
+    # pass 2 starts from dtype-rounded partials: one extra rounding step
+    tol2 = 1e-4 if dtype == torch.float32 else \
+        scaled.abs().max().item() * 2 ** -6
+    assert torch.allclose(got.float().cpu(), scaled, atol=tol2, rtol=0.05), \
+        (got.float().cpu() - scaled).abs().max()
+
+
+@pytest.mark.parametrize("dtype,D", _EDGE_SHAPES)
+def test_edge_dot_shapes(ladder_csr, dtype, D):
+    rowptr, colidx = ladder_csr
+    torch.manual_seed(47)
+    dy = torch.randn(64, D).to(dtype)
+    x = torch.randn(200, D).to(dtype)
+    want = ref.edge_dot(dy.float(), x.float(), rowptr, colidx)
+    dw = torch.empty(colidx.numel(), dtype=torch.float32, device=DEV)
+    _ext().edge_dot(dw, dy.to(DEV), x.to(DEV), rowptr.to(DEV),
+                    colidx.to(DEV))
+    tol = 1e-3 if dtype == torch.float32 else \
+        want.abs().max().item() * 2 ** -6 + 5e-2
+    assert torch.allclose(dw.cpu(), want, atol=tol, rtol=0.05), \
+        (dw.cpu() - want).abs().max()
+
+
+def test_segment_softmax_ladder_csr(ladder_csr):
+    """edge_softmax and attention_softmax fwd + bwd vs the CPU path on
+    the ladder CSR (empty row, rows shorter and longer than a team)."""
+    rowptr, colidx = ladder_csr
+    roe = torch.repeat_interleave(torch.arange(64), rowptr[1:] - rowptr[:-1])
+    rp, ci, roe_d = rowptr.to(DEV), colidx.to(DEV), roe.to(DEV)
+    torch.manual_seed(53)
+    E = colidx.numel()
+    s = torch.randn(E) * 3
+    gy = torch.randn(E)
+    sc = s.clone().requires_grad_(True)
+    a_c = F._EdgeSoftmax.apply(sc, rowptr, roe)
+    a_c.backward(gy)
+    sg = s.to(DEV).requires_grad_(True)
+    a_g = F._EdgeSoftmax.apply(sg, rp, roe_d)
+    a_g.backward(gy.to(DEV))
+    assert torch.allclose(a_g.cpu(), a_c, atol=1e-6), \
+        (a_g.cpu() - a_c).abs().max()
+    assert torch.allclose(sg.grad.cpu(), sc.grad, atol=1e-6), \
+        (sg.grad.cpu() - sc.grad).abs().max()
+
+    src_c = torch.randn(200, requires_grad=True)
+    dst_c = torch.randn(64, requires_grad=True)
+    a_c = F._AttentionSoftmax.apply(src_c, dst_c, rowptr, colidx, roe, 0.2)
+    a_c.backward(gy)
+    src_g = src_c.detach().to(DEV).requires_grad_(True)
+    dst_g = dst_c.detach().to(DEV).requires_grad_(True)
+    a_g = F._AttentionSoftmax.apply(src_g, dst_g, rp, ci, roe_d, 0.2)
+    a_g.backward(gy.to(DEV))
+    assert torch.allclose(a_g.cpu(), a_c, atol=1e-6)
+    assert torch.allclose(src_g.grad.cpu(), src_c.grad, atol=1e-4), \
+        (src_g.grad.cpu() - src_c.grad).abs().max()
+    assert torch.allclose(dst_g.grad.cpu(), dst_c.grad, atol=1e-5)
+    assert dst_g.grad[0].item() == 0.0  # empty row
+
+
+def test_gemm_atb_fp32_wide_tile():
+    """fp32 on the 128x128 dW tile, ragged on both tile edges; two calls
+    into equal non-zero C are bit-identical and have accumulated."""
+    torch.manual_seed(59)
+    R, Ka, N = 700, 136, 129
+    A = torch.randn(R, Ka)
+    B = torch.randn(R, N) * 0.1
+    C0 = torch.randn(Ka, N)
+    want = C0 + A.t() @ B
+    Ad, Bd = A.to(DEV), B.to(DEV)
+    outs = []
+    for _ in range(2):
+        C = C0.to(DEV)
+        _ext().gemm_atb(C, Ad, Bd)
+        outs.append(C.cpu())
+    assert torch.equal(outs[0], outs[1])
+    tol = want.abs().max().item() * 1e-5 + 1e-3
+    assert torch.allclose(outs[0], want, atol=tol, rtol=1e-4), \
+        (outs[0] - want).abs().max()
+
+
+def test_att_softmax_bwd_rejects_bad_args(ladder_csr):
+    rowptr, colidx = (t.to(DEV) for t in ladder_csr)
+    E = colidx.numel()
+    f = lambda n: torch.zeros(n, device=DEV)
+    with pytest.raises(RuntimeError):  # CPU s_src
+        _ext().att_softmax_bwd(f(200), f(64), f(E), f(E), torch.zeros(200),
+                               f(64), rowptr, colidx, 0.2)
+    with pytest.raises(RuntimeError):  # non-contiguous alpha
+        _ext().att_softmax_bwd(f(200), f(64), f(E), f(2 * E)[::2], f(200),
+                               f(64), rowptr, colidx, 0.2)
