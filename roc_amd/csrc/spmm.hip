@@ -17,6 +17,9 @@
 //  - rows are visited in degree-descending order (row_order) so hub rows
 //    start first and the skew tail is hidden (Reddit max degree >> mean)
 //  - wide feature dims are column-tiled across blockIdx.y
+//  - source-strip passes (fp32 partials) start the rows that are heavy in
+//    their strip first, from a short list, and the last pass stores the
+//    bf16 result itself (HEAVY / FINAL variants of spmm_kernel)
 //
 // The vector path and the (rare) partial-unit tail path are fully
 // separated: the hot path's per-slot buffers are only ever statically
@@ -173,13 +176,37 @@ __device__ void row_accum_tail(
 // fp32 partial buffer is touched once per much-wider source strip).
 // `weight` is deg_src (indexed by source) or edge_val (indexed by edge)
 // as W says; unused for Weight::kNone.
-template <typename T, typename OT, int TEAM, int UN, bool BUF, Weight W>
+//
+// Two compile-time variants serve the strip passes (bf16 x, fp32
+// partials, no weight); with both off the kernel is the plain one:
+//  HEAVY  heavy-first schedule. `heavy_rows` lists exactly the rows with
+//         e1 - e0 >= heavy_min, longest first. A team takes its share of
+//         that list before its natural sweep, and the sweep skips those
+//         rows by the rowptr values it has loaded anyway: light rows pay
+//         no indirection. The list is dealt out a wave at a time: the
+//         64/TEAM teams of one wave take consecutive entries (rows of
+//         about equal length, so no team idles while its wave-mates
+//         finish a long row — measured 3-11% of a pass over dealing
+//         single entries, profiles/r38), and consecutive waves' worth go
+//         to consecutive workgroups, so the longest rows start in the
+//         first resident wave on different CUs. One loop serves both
+//         phases, so a wave whose teams are in different phases still
+//         shares the gather code.
+//         Which team owns a row never changes the row's own summation
+//         order, so results equal the plain pass bit for bit.
+//  FINAL  last strip pass: the finished row goes to `final_out` as bf16
+//         (after the optional deg_dst scale) and the fp32 partials are
+//         only read — the separate cast pass over memory disappears.
+template <typename T, typename OT, int TEAM, int UN, bool BUF, Weight W,
+          bool HEAVY = false, bool FINAL = false>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(
     OT* __restrict__ out, const T* __restrict__ x,
     const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
     const float* __restrict__ deg_dst, const float* __restrict__ weight,
     const int* __restrict__ row_order, int num_rows, int64_t ld,
-    int64_t col_base, int64_t col_end, bool accumulate, unsigned x_bytes) {
+    int64_t col_base, int64_t col_end, bool accumulate, unsigned x_bytes,
+    const int* __restrict__ heavy_rows, int num_heavy, int heavy_min,
+    unsigned short* __restrict__ final_out) {
   constexpr int EPU = EltTraits<T>::kPerVec;
   const RowTeam<TEAM> rt;
 
@@ -190,10 +217,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
       full ? EPU : (col0 < col_end ? (int)(col_end - col0) : 0);
 
   if (full) {
-    for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
-      const int row = row_order ? row_order[ri] : ri;
-      const int64_t e0 = rowptr[row];
-      const int64_t e1 = rowptr[row + 1];
+    auto do_row = [&](int row, int64_t e0, int64_t e1) {
       float acc[EPU];
       OT* o = out + (int64_t)row * ld + col0;
       if (accumulate) {  // strip / halo-overlap pass 2: from partials
@@ -218,9 +242,40 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] *= s;
       }
-      store_vec(o, acc);
+      if constexpr (FINAL) store_vec(final_out + (int64_t)row * ld + col0, acc);
+      else store_vec(o, acc);
+    };
+    if constexpr (HEAVY) {
+      // list entry h: wave-sized runs of entries go round the workgroups
+      constexpr int TPW = 64 / TEAM;  // teams per wave
+      const int lt = (int)threadIdx.x / TEAM;
+      int h = ((lt / TPW) * (int)gridDim.x + (int)blockIdx.x) * TPW + lt % TPW;
+      int ri = rt.team;
+      for (;;) {
+        int row;
+        const bool from_list = h < num_heavy;
+        if (from_list) {
+          row = heavy_rows[h];
+          h += rt.nteams;
+          if ((unsigned)row >= (unsigned)num_rows) continue;  // bad entry
+        } else {
+          if (ri >= num_rows) break;
+          row = ri;
+          ri += rt.nteams;
+        }
+        const int64_t e0 = rowptr[row];
+        const int64_t e1 = rowptr[row + 1];
+        if (!from_list && e1 - e0 >= heavy_min) continue;  // done above
+        do_row(row, e0, e1);
+      }
+    } else {
+      for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
+        const int row = row_order ? row_order[ri] : ri;
+        do_row(row, rowptr[row], rowptr[row + 1]);
+      }
     }
   } else if (nvalid > 0) {
+    // cold path: natural sweep whatever the schedule variant
     for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
       const int row = row_order ? row_order[ri] : ri;
       float acc[EPU];
@@ -230,7 +285,12 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
       row_accum_tail<T, W>(acc, x, ld, col0, nvalid, colidx, weight,
                            rowptr[row], rowptr[row + 1]);
       const float s = deg_dst ? deg_dst[row] : 1.f;
-      for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
+      if constexpr (FINAL) {
+        unsigned short* fo = final_out + (int64_t)row * ld + col0;
+        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, fo + j);
+      } else {
+        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
+      }
     }
   }
 }
@@ -270,12 +330,24 @@ static const SpmmKnobs& spmm_knobs() {
 // The one spmm_kernel launch: geometry from the column window, gather
 // engine from the matrix size, TEAM and BUF lifted to template constants.
 // team_override == 0 picks the team by width.
-template <typename T, typename OT, int UN, Weight W>
+// The strip-pass extras of one launch (see spmm_kernel): the heavy-first
+// list with its threshold, and the bf16 destination of a final pass.
+struct StripPass {
+  bool heavy = false;  // heavy_rows given (it may be empty)
+  const int* heavy_rows = nullptr;
+  int num_heavy = 0;
+  int heavy_min = 0;
+  unsigned short* final_out = nullptr;
+};
+
+template <typename T, typename OT, int UN, Weight W, bool HEAVY = false,
+          bool FINAL = false>
 void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
                  const int* colidx, const float* deg_dst, const float* weight,
                  const int* row_order, int num_rows, int64_t ld,
                  int64_t col_base, int64_t col_end, bool accumulate,
-                 size_t x_elems, int team_override, hipStream_t stream) {
+                 size_t x_elems, int team_override, hipStream_t stream,
+                 const StripPass& sp = {}) {
   constexpr int EPU = EltTraits<T>::kPerVec;
   const int64_t units = (col_end - col_base + EPU - 1) / EPU;
   const int team = team_override ? team_override : row_team_size(units);
@@ -292,10 +364,10 @@ void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
     dispatch_bool(buf, [&](auto buf_c) {
       hipLaunchKernelGGL(
           (spmm_kernel<T, OT, decltype(team_c)::value, UN,
-                       decltype(buf_c)::value, W>),
+                       decltype(buf_c)::value, W, HEAVY, FINAL>),
           grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
           weight, row_order, num_rows, ld, col_base, col_end, accumulate,
-          x_bytes);
+          x_bytes, sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out);
     });
   });
 }
@@ -429,9 +501,42 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           torch::Tensor colidx, c10::optional<torch::Tensor> deg_dst,
           c10::optional<torch::Tensor> deg_src,
           c10::optional<torch::Tensor> row_order, bool accumulate,
-          int64_t col_base, int64_t ncols) {
+          int64_t col_base, int64_t ncols,
+          c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
+          c10::optional<torch::Tensor> final_out) {
   ROC_CHECK_DEV_CONT(out);
   ROC_CHECK_DEV_CONT(x);
+  // strip-pass extras: heavy-first schedule and fused final bf16 store
+  StripPass sp;
+  if (heavy_rows.has_value() || final_out.has_value()) {
+    TORCH_CHECK(out.scalar_type() == torch::kFloat32 &&
+                    x.scalar_type() == torch::kBFloat16 &&
+                    !deg_src.has_value(),
+                "heavy_rows / final_out are strip-pass options: bf16 x, "
+                "fp32 out, no deg_src");
+  }
+  if (heavy_rows.has_value()) {
+    ROC_CHECK_DEV_CONT(*heavy_rows);
+    TORCH_CHECK(heavy_rows->scalar_type() == torch::kInt32,
+                "heavy_rows must be int32");
+    TORCH_CHECK(!row_order.has_value(),
+                "heavy_rows and row_order are exclusive");
+    TORCH_CHECK(heavy_min >= 0 && heavy_min <= INT_MAX, "bad heavy_min");
+    sp.heavy = true;
+    sp.heavy_rows = heavy_rows->data_ptr<int>();
+    sp.num_heavy = (int)heavy_rows->numel();
+    sp.heavy_min = (int)heavy_min;
+  }
+  if (final_out.has_value()) {
+    ROC_CHECK_DEV_CONT(*final_out);
+    TORCH_CHECK(final_out->scalar_type() == torch::kBFloat16,
+                "final_out must be bf16");
+    TORCH_CHECK(final_out->sizes() == out.sizes(),
+                "final_out shape mismatch");
+    TORCH_CHECK(col_base == 0 && ncols == 0,
+                "final_out needs a whole-row pass");
+    sp.final_out = (unsigned short*)final_out->data_ptr();
+  }
   TORCH_CHECK(out.scalar_type() == x.scalar_type() ||
                   (out.scalar_type() == torch::kFloat32 &&
                    x.scalar_type() == torch::kBFloat16),
@@ -455,12 +560,30 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
       // (fp32 x with bf16 out is rejected above and never instantiated)
       if constexpr (sizeof(OT) >= sizeof(T)) {
         auto go = [&](auto un_c, auto w_c) {
-          launch_spmm<T, OT, decltype(un_c)::value, decltype(w_c)::value>(
-              (OT*)out.data_ptr(), (const T*)x.data_ptr(),
-              rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
-              opt_ptr<float>(deg_dst), ds, opt_ptr<int>(row_order), num_rows,
-              D, col_base, col_end, accumulate, (size_t)x.numel(),
-              kn.team_override, stream);
+          constexpr int UN = decltype(un_c)::value;
+          constexpr Weight W = decltype(w_c)::value;
+          auto launch = [&](auto heavy_c, auto final_c) {
+            launch_spmm<T, OT, UN, W, decltype(heavy_c)::value,
+                        decltype(final_c)::value>(
+                (OT*)out.data_ptr(), (const T*)x.data_ptr(),
+                rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
+                opt_ptr<float>(deg_dst), ds, opt_ptr<int>(row_order),
+                num_rows, D, col_base, col_end, accumulate,
+                (size_t)x.numel(), kn.team_override, stream, sp);
+          };
+          // the strip-pass variants exist for bf16 -> fp32, no weight only
+          // (checked above), so nothing else is instantiated with them
+          if constexpr (std::is_same_v<T, unsigned short> &&
+                        std::is_same_v<OT, float> && W == Weight::kNone) {
+            if (sp.heavy || sp.final_out) {
+              dispatch_bool(sp.heavy, [&](auto heavy_c) {
+                dispatch_bool(sp.final_out != nullptr,
+                              [&](auto final_c) { launch(heavy_c, final_c); });
+              });
+              return;
+            }
+          }
+          launch(std::false_type{}, std::false_type{});
         };
         auto by_weight = [&](auto un_c) {
           if (ds) go(un_c, std::integral_constant<Weight, Weight::kSrc>{});

@@ -108,7 +108,7 @@ def _hip(x: torch.Tensor) -> bool:
 # ScatterGather (CSR SpMM neighbor aggregation) — the hot op
 # ---------------------------------------------------------------------------
 
-def _strip_spmm(x, strips, num_rows, row_scale):
+def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0):
     """Source-strip-blocked SpMM: each pass gathers from an L2-resident
     source window; partials accumulate in fp32 (one rounding total —
     same numerics as single-pass). Wide feature dims additionally sweep
@@ -116,7 +116,10 @@ def _strip_spmm(x, strips, num_rows, row_scale):
     gather working set (rows x cols bytes) while the fp32 partial buffer
     is re-read/re-written 4x less often — partial traffic, not gathers,
     was the next bound (profiles/r23). The epilogue casts back to
-    x.dtype and applies the optional fp32 row_scale."""
+    x.dtype and applies the optional fp32 row_scale; for bf16 the last
+    whole-row pass does that itself (final_out) and no cast pass runs.
+    heavy: per-strip heavy-first row lists with their threshold
+    (partition.build_strip_heavy), bf16 passes only."""
     D = x.shape[1]
     out32 = torch.empty(num_rows, D, dtype=torch.float32, device=x.device)
     ph = _phase_cols()
@@ -124,10 +127,24 @@ def _strip_spmm(x, strips, num_rows, row_scale):
         phases = [(p, ph) for p in range(0, D, ph)]
     else:
         phases = [(0, 0)]  # one whole-row phase
+    bf16 = x.dtype == torch.bfloat16
+    fuse_final = bf16 and D % 8 == 0 and phases == [(0, 0)]
+    if not bf16:
+        heavy = None
+    out = None
     for col_base, ncols in phases:
         for i, (srp, sci) in enumerate(strips):
-            _C.spmm(out32, x, srp, sci, None, None, None, i > 0,
-                    col_base, ncols)
+            hv = heavy[i] if heavy is not None else None
+            if fuse_final and i == len(strips) - 1:
+                out = torch.empty(num_rows, D, dtype=torch.bfloat16,
+                                  device=x.device)
+                _C.spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
+                        0, 0, hv, heavy_min, out)
+            else:
+                _C.spmm(out32, x, srp, sci, None, None, None, i > 0,
+                        col_base, ncols, hv, heavy_min)
+    if out is not None:
+        return out
     if x.dtype == torch.bfloat16 and D % 8 == 0:
         out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
         _C.cast_rowscale(out, out32, row_scale)  # fused epilogue
@@ -145,12 +162,15 @@ class _SpMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, num_rows, num_ext,
                 deg_dst, deg_src, row_order, t_row_order,
-                fwd_strips=None, bwd_strips=None):
+                fwd_strips=None, bwd_strips=None, fwd_heavy=None,
+                bwd_heavy=None, heavy_min=0):
         ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src, t_row_order)
         ctx.num_ext = num_ext
         ctx.bwd_strips = bwd_strips
+        ctx.bwd_heavy = (bwd_heavy, heavy_min)
         if _hip(x) and fwd_strips is not None and deg_src is None:
-            out = _strip_spmm(x, fwd_strips, num_rows, deg_dst)
+            out = _strip_spmm(x, fwd_strips, num_rows, deg_dst, fwd_heavy,
+                              heavy_min)
         elif _hip(x):
             out = torch.empty(num_rows, x.shape[1], dtype=x.dtype, device=x.device)
             _C.spmm(out, x, rowptr, colidx, deg_dst, deg_src, row_order)
@@ -176,7 +196,8 @@ class _SpMM(torch.autograd.Function):
                 _C.rowscale(tmp, dy, deg_dst)
                 dy = tmp
             if ctx.bwd_strips is not None and deg_src is None:
-                dx = _strip_spmm(dy, ctx.bwd_strips, ctx.num_ext, None)
+                dx = _strip_spmm(dy, ctx.bwd_strips, ctx.num_ext, None,
+                                 *ctx.bwd_heavy)
             else:
                 dx = torch.empty(ctx.num_ext, dy.shape[1], dtype=dy.dtype,
                                  device=dy.device)
@@ -188,7 +209,7 @@ class _SpMM(torch.autograd.Function):
             dx = ref.spmm(yin, t_rowptr, t_colidx, ctx.num_ext)
             if deg_src is not None:
                 dx = dx * deg_src.unsqueeze(1).to(dx.dtype)
-        return (dx,) + (None,) * 12
+        return (dx,) + (None,) * 15
 
 
 class _SpMMEdge(torch.autograd.Function):
@@ -392,6 +413,9 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
         shard.n_local, shard.n_ext, deg_dst, deg_src,
         shard.row_order, shard.t_row_order,
         shard.fwd_strips, shard.bwd_strips,
+        getattr(shard, "fwd_strip_heavy", None),
+        getattr(shard, "bwd_strip_heavy", None),
+        getattr(shard, "strip_heavy_min", 0),
     )
 
 

@@ -102,6 +102,12 @@ class GraphShard:
     # build_strip_plan; large local CSRs only) ------------------------
     fwd_strips: Optional[list] = None  # [(rowptr, colidx), ...]
     bwd_strips: Optional[list] = None  # same, for the transpose CSR
+    # heavy-first schedule of the strip passes (build_strip_heavy): per
+    # strip, the int32 rows whose segment has >= strip_heavy_min edges,
+    # longest first. None = natural sweep only.
+    fwd_strip_heavy: Optional[list] = None
+    bwd_strip_heavy: Optional[list] = None
+    strip_heavy_min: int = 0
 
     def to(self, device) -> "GraphShard":
         d = {}
@@ -112,6 +118,8 @@ class GraphShard:
                 v = v.to(device)
             elif isinstance(v, list) and v and isinstance(v[0], tuple):
                 v = [tuple(t.to(device) for t in tup) for tup in v]
+            elif isinstance(v, list) and v and isinstance(v[0], torch.Tensor):
+                v = [t.to(device) for t in v]
             d[k] = v
         return GraphShard(**d)
 
@@ -197,6 +205,39 @@ def build_strip_plan(rowptr: torch.Tensor, colidx: torch.Tensor,
             sci = np.empty(0, dtype=ci.dtype)
         strips.append((torch.from_numpy(srp), torch.from_numpy(sci)))
     return strips
+
+
+# swept 16..512 at Reddit shape (profiles/r38): 128 lists 3.4% of the
+# rows and is within 0.4% (D=256) / 5% (D=64) of the best threshold
+HEAVY_MIN_DEFAULT = 128
+_HEAVY_MIN: Optional[int] = None
+
+
+def strip_heavy_min() -> int:
+    """Edges per strip segment from which a row counts as heavy and is
+    started first by its strip pass (ROC_SPMM_HEAVY_MIN, 0 = off).
+    Pinned at first use like the other SpMM geometry knobs: the lists
+    and the threshold a kernel skips by must come from one value."""
+    global _HEAVY_MIN
+    if _HEAVY_MIN is None:
+        _HEAVY_MIN = max(0, int(os.environ.get("ROC_SPMM_HEAVY_MIN",
+                                               str(HEAVY_MIN_DEFAULT))))
+    return _HEAVY_MIN
+
+
+def build_strip_heavy(strips, heavy_min: int):
+    """Heavy-first lists for a strip plan: for each strip the rows whose
+    segment holds >= heavy_min edges, as int32, longest segment first
+    (ties in row order). The strip kernel starts these before its
+    natural sweep and skips them there by the same threshold, so list
+    and threshold always travel together."""
+    heavy = []
+    for srp, _ in strips:
+        seg = np.diff(srp.numpy())
+        rows = np.nonzero(seg >= heavy_min)[0]
+        rows = rows[np.argsort(-seg[rows], kind="stable")]
+        heavy.append(torch.from_numpy(rows.astype(np.int32)))
+    return heavy
 
 
 def edge_tensor(shard: GraphShard, dim: Optional[int] = None,
@@ -555,6 +596,13 @@ def build_shard_from_window(rowptr_full: torch.Tensor,
                                                   n_ext, strip_w)
         shard_kw["bwd_strips"] = build_strip_plan(t_rowptr, t_colidx,
                                                   n_local, strip_w)
+        heavy_min = strip_heavy_min()
+        if heavy_min > 0:
+            shard_kw["fwd_strip_heavy"] = build_strip_heavy(
+                shard_kw["fwd_strips"], heavy_min)
+            shard_kw["bwd_strip_heavy"] = build_strip_heavy(
+                shard_kw["bwd_strips"], heavy_min)
+            shard_kw["strip_heavy_min"] = heavy_min
 
     return GraphShard(
         rank=rank, world_size=world_size, bounds=list(bounds),
