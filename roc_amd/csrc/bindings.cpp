@@ -36,6 +36,13 @@ void spmm_edge(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
                c10::optional<torch::Tensor> row_order, bool accumulate);
 void edge_dot(torch::Tensor dw, torch::Tensor dy, torch::Tensor x,
               torch::Tensor rowptr, torch::Tensor colidx);
+void seg_max_fwd(torch::Tensor out, c10::optional<torch::Tensor> arg,
+                 torch::Tensor x, torch::Tensor rowptr, torch::Tensor colidx,
+                 c10::optional<torch::Tensor> row_order, bool is_min);
+void seg_max_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor arg,
+                 torch::Tensor t_rowptr, torch::Tensor t_colidx,
+                 torch::Tensor t_eperm,
+                 c10::optional<torch::Tensor> t_row_order);
 void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
                       torch::Tensor rowptr);
 void edge_softmax_bwd(torch::Tensor ds, torch::Tensor dalpha,
@@ -100,6 +107,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("accumulate") = false);
   m.def("edge_dot", &edge_dot,
         "dw[e] = <dy[row_e], x[col_e]> (edge-value gradient)");
+  m.def("seg_max_fwd", &seg_max_fwd,
+        "CSR segment max/min aggregation; arg = winning forward edge index",
+        pybind11::arg("out"), pybind11::arg("arg"), pybind11::arg("x"),
+        pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order") = pybind11::none(),
+        pybind11::arg("is_min") = false);
+  m.def("seg_max_bwd", &seg_max_bwd,
+        "segment max/min gradient: gather of dy over the transpose CSR",
+        pybind11::arg("dx"), pybind11::arg("dy"), pybind11::arg("arg"),
+        pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
+        pybind11::arg("t_eperm"),
+        pybind11::arg("t_row_order") = pybind11::none());
   m.def("edge_softmax_fwd", &edge_softmax_fwd,
         "per-row segment softmax over edge scores (GAT attention)");
   m.def("edge_softmax_bwd", &edge_softmax_bwd);

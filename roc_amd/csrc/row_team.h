@@ -1,4 +1,5 @@
-// Row-team frame shared by the CSR kernels (spmm.hip, edge_softmax.hip).
+// Row-team frame shared by the CSR kernels (spmm.hip, seg_max.hip,
+// edge_softmax.hip).
 //
 // A team of TEAM contiguous lanes (a power of two <= 64, so a team never
 // straddles a wave64) owns one CSR row at a time; teams grid-stride over

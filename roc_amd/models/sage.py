@@ -1,4 +1,4 @@
-"""GraphSAGE (mean aggregator, concat variant).
+"""GraphSAGE (mean aggregator by default, concat variant).
 
 h' = relu( W_self·h_v  +  W_neigh·mean_{u in N(v)} h_u )
 
@@ -8,6 +8,14 @@ the NARROWER of (input, output) width — W_neigh is applied before the
 exchange+aggregation on shrinking layers and after them on widening
 ones (mean_u(h W) == (mean_u h) W) — so the gather stream and the halo
 exchange always move the skinnier rows.
+
+aggr="max" | "min" swaps the mean for the elementwise extremum over the
+in-neighbors (the SAGEConv max form):
+
+h' = relu( W_self·h_v  +  W_neigh·ext_{u in N(v)} h_u )
+
+An extremum does not commute with W_neigh, so that layer always
+aggregates first, at the input width, and ROC_ADAPTIVE_AGG does not apply.
 """
 from __future__ import annotations
 
@@ -19,8 +27,13 @@ from ..parallel.aggregate import aggregate
 
 
 class GraphSAGE(torch.nn.Module):
-    def __init__(self, dims, dropout: float = 0.5, seed: int = 1):
+    def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
+                 aggr: str = "mean"):
         super().__init__()
+        if aggr not in ("mean", "max", "min"):
+            raise ValueError(
+                f"aggr must be 'mean', 'max' or 'min', got {aggr!r}")
+        self.aggr = aggr
         self.dims = list(dims)
         self.p = float(dropout)
         self.w_self = torch.nn.ParameterList()
@@ -48,7 +61,10 @@ class GraphSAGE(torch.nn.Module):
         h_self = F.linear(h, self.w_self[i])
         wn = self.w_neigh[i]
         from .gcn import _adaptive_agg
-        if wn.shape[0] < wn.shape[1] and _adaptive_agg():
+        if self.aggr != "mean":
+            hn = aggregate(h, shard, group=group, reduce=self.aggr)
+            hn = F.linear(hn, wn)
+        elif wn.shape[0] < wn.shape[1] and _adaptive_agg():
             # widening layer: mean-aggregate first at the narrower
             # input width (mean_u(h W) == (mean_u h) W) — smaller
             # gather stream and halo exchange
@@ -75,7 +91,10 @@ class GraphSAGE(torch.nn.Module):
             h = F.dropout(x, self.p, self.training, call_id=i)
             h_self = F.linear(h[:blk.n_dst].contiguous(), self.w_self[i])
             wn = self.w_neigh[i]
-            if wn.shape[0] < wn.shape[1] and _adaptive_agg():
+            if self.aggr != "mean":
+                hn = F.scatter_gather_reduce(h, blk, self.aggr)
+                hn = F.linear(hn, wn)
+            elif wn.shape[0] < wn.shape[1] and _adaptive_agg():
                 hn = F.scatter_gather(h, blk, dst_scale=blk.inv_deg)
                 hn = F.linear(hn, wn)
             else:

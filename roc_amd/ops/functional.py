@@ -419,6 +419,103 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
     )
 
 
+class _SegReduce(torch.autograd.Function):
+    """out[v] = max / min over in-neighbors of x[u] (seg_max.hip). arg is
+    the winning forward edge per (row, column); the backward is a
+    deterministic gather over the transpose CSR that adds dy[v, j] to
+    source u where arg[v, j] names the forward edge of the transposed
+    edge (u, v) — no atomics. arg is produced and saved only when x needs
+    a gradient (or the caller asks for it); t_eperm is a thunk for the
+    int32 transposed-edge -> forward-edge map and is called only then."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, t_eperm,
+                num_rows, num_src, is_min, row_order, t_row_order,
+                return_arg):
+        need_grad = ctx.needs_input_grad[0]
+        x = x.contiguous()
+        arg = None
+        if _hip(x):
+            out = torch.empty(num_rows, x.shape[1], dtype=x.dtype,
+                              device=x.device)
+            if need_grad or return_arg:
+                arg = torch.empty(num_rows, x.shape[1], dtype=torch.int32,
+                                  device=x.device)
+            _C.seg_max_fwd(out, arg, x, rowptr, colidx, row_order, is_min)
+        else:
+            out, arg = ref.seg_max(x, rowptr, colidx, num_rows,
+                                   "min" if is_min else "max")
+        ctx.num_src = num_src
+        if need_grad:
+            if x.is_cuda:
+                ctx.save_for_backward(arg, t_rowptr, t_colidx, t_eperm(),
+                                      t_row_order)
+            else:
+                ctx.save_for_backward(arg, rowptr, colidx)
+        if not return_arg:
+            arg = torch.empty(0, dtype=torch.int32, device=x.device)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dy, _darg):
+        dy = dy.contiguous()
+        if _hip(dy):
+            arg, t_rowptr, t_colidx, t_eperm, t_row_order = ctx.saved_tensors
+            dx = torch.empty(ctx.num_src, dy.shape[1], dtype=dy.dtype,
+                             device=dy.device)
+            _C.seg_max_bwd(dx, dy, arg, t_rowptr, t_colidx, t_eperm,
+                           t_row_order)
+        else:
+            arg, rowptr, colidx = ctx.saved_tensors
+            dx = ref.seg_max_grad(dy, arg, rowptr, colidx, ctx.num_src)
+        return (dx,) + (None,) * 11
+
+
+def _check_reduce(reduce: str) -> bool:
+    if reduce not in ("max", "min"):
+        raise ValueError(f"reduce must be 'max' or 'min', got {reduce!r}")
+    return reduce == "min"
+
+
+def seg_reduce_csr(x, rowptr, colidx, t_rowptr, t_colidx, t_eperm, num_rows,
+                   num_src, reduce="max", row_order=None, t_row_order=None,
+                   return_arg=False):
+    """scatter_gather_reduce over an explicit CSR / transpose-CSR pair.
+    t_eperm: a callable returning the int32 [E] map from transposed edge
+    to forward edge (the stable argsort of colidx)."""
+    if x.dim() != 2 or x.shape[0] != num_src:
+        # colidx indexes x unchecked on the GPU: a short x reads out of bounds
+        raise ValueError(f"x must be [{num_src}, D], got {tuple(x.shape)}")
+    out, arg = _SegReduce.apply(
+        x, rowptr, colidx, t_rowptr, t_colidx, t_eperm, num_rows, num_src,
+        _check_reduce(reduce), row_order, t_row_order, return_arg)
+    return (out, arg) if return_arg else out
+
+
+def scatter_gather_reduce(x, shard, reduce: str = "max",
+                          return_arg: bool = False):
+    """Neighbor max / min aggregation over the shard's local CSR (the
+    reference's declared-but-dead AGGR_MAX / AGGR_MIN).
+
+    x: [n_ext, D] halo-extended features. Returns [n_local, D] in x's
+    dtype; every output element is one of the inputs bit for bit. Among
+    equal values the first edge in CSR order wins and takes the whole
+    gradient; rows without edges give 0 and pass no gradient.
+    return_arg=True also returns arg, int32 [n_local, D]: the local CSR
+    edge index of each winner (-1 on empty rows). `shard` may be a
+    GraphShard or a sampling Block; a Block has no cached edge
+    permutation, so its backward map is computed per call."""
+    cached = getattr(shard, "t_edge_perm32", None)
+    if cached is None:
+        def cached():
+            return torch.argsort(shard.colidx.long(), stable=True).int()
+    return seg_reduce_csr(
+        x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+        cached, shard.n_local, shard.n_ext, reduce, shard.row_order,
+        shard.t_row_order, return_arg)
+
+
 # ---------------------------------------------------------------------------
 # InDegreeNorm
 # ---------------------------------------------------------------------------

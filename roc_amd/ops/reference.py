@@ -55,6 +55,60 @@ def edge_dot(dy: torch.Tensor, x: torch.Tensor, rowptr: torch.Tensor,
     return (dy[dst].float() * x[colidx.to(torch.long)].float()).sum(dim=1)
 
 
+def seg_max(x: torch.Tensor, rowptr: torch.Tensor, colidx: torch.Tensor,
+            num_rows: int, reduce: str = "max"):
+    """out[v, j] = max (or min) over the edges e of row v of x[colidx[e], j];
+    arg[v, j] (int32) = the CSR edge index e of the winner. Among equal
+    values the FIRST edge in CSR order wins; an empty row gives out = 0,
+    arg = -1. The reference declares AGGR_MAX / AGGR_MIN (`gnn.h:75-79`)
+    and implements neither. NaN inputs are out of contract.
+
+    arg names an edge, not a source row, so that duplicate (u, v) edges
+    route the gradient once. out is read back through arg, so it carries
+    the winning input's own bits (low-precision x is compared in fp32)."""
+    if reduce not in ("max", "min"):
+        raise ValueError(f"reduce must be 'max' or 'min', got {reduce!r}")
+    E, D = int(colidx.numel()), x.shape[1]
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=x.device), deg)
+    wide = x.dtype in (torch.float32, torch.float64)
+    vals = (x if wide else x.float())[colidx.to(torch.long)]  # [E, D]
+    idx = dst.unsqueeze(1).expand(E, D)
+    best = torch.zeros(num_rows, D, dtype=vals.dtype, device=x.device)
+    best = best.scatter_reduce(0, idx, vals,
+                               reduce="amax" if reduce == "max" else "amin",
+                               include_self=False)
+    eid = torch.arange(E, dtype=torch.long, device=x.device).unsqueeze(1)
+    cand = torch.where(vals == best[dst], eid.expand(E, D),
+                       torch.full((), E, dtype=torch.long, device=x.device))
+    arg = torch.full((num_rows, D), E, dtype=torch.long, device=x.device)
+    arg = arg.scatter_reduce(0, idx, cand, reduce="amin", include_self=True)
+    empty = (deg == 0).unsqueeze(1)
+    arg = arg.masked_fill(empty, 0)
+    if E > 0:
+        out = torch.gather(vals, 0, arg).masked_fill(empty, 0)
+    else:
+        out = torch.zeros(num_rows, D, dtype=vals.dtype, device=x.device)
+    arg = arg.masked_fill(empty, -1).to(torch.int32)
+    return out.to(x.dtype), arg
+
+
+def seg_max_grad(dy: torch.Tensor, arg: torch.Tensor, rowptr: torch.Tensor,
+                 colidx: torch.Tensor, num_src: int) -> torch.Tensor:
+    """Gradient of seg_max wrt x: dy[v, j] goes, whole, to source row
+    colidx[arg[v, j]] (first-edge routing — torch's own amax backward
+    splits ties evenly, so it is not the oracle here). rowptr is unused:
+    arg already names the edge."""
+    dx = torch.zeros(num_src, dy.shape[1], dtype=dy.dtype, device=dy.device)
+    if colidx.numel() == 0 or dy.numel() == 0:
+        return dx
+    hit = arg >= 0
+    src = colidx.to(torch.long)[arg.to(torch.long).clamp(min=0)]
+    dx.scatter_add_(0, src, torch.where(hit, dy, torch.zeros_like(dy)))
+    return dx
+
+
 def degnorm(x: torch.Tensor, deg: torch.Tensor) -> torch.Tensor:
     """out[v] = x[v] / sqrt(indeg(v))  (reference `graphnorm_kernel.cu:19-57`)."""
     return x * torch.rsqrt(deg.clamp(min=1.0)).unsqueeze(1).to(x.dtype)

@@ -154,10 +154,72 @@ class _GatherAggregate(torch.autograd.Function):
         return dx_pad[:shard.n_local].contiguous(), None, None, None
 
 
-def aggregate(x, shard, dst_scale=None, group=None):
-    """Distributed neighbor sum-aggregation of the LOCAL feature block
-    (+ optional fused dst-side degree scale). Returns [n_local, D]."""
+class _GatherBlocks(torch.autograd.Function):
+    """Differentiable exchange for the allgather-mode max/min path:
+    forward all_gathers the padded local blocks into the gather space
+    [ws * ag_max_rows, D]; backward reduce_scatters the gather-space
+    gradient back to its owners."""
+
+    @staticmethod
+    def forward(ctx, x, shard, group):
+        ctx.shard = shard
+        ctx.group = group
+        D = x.shape[1]
+        mr = shard.ag_max_rows
+        send = x
+        if x.shape[0] < mr:  # pad the block to the common size
+            send = torch.zeros(mr, D, dtype=x.dtype, device=x.device)
+            send[:x.shape[0]] = x
+        gathered = torch.empty(shard.world_size * mr, D, dtype=x.dtype,
+                               device=x.device)
+        dist.all_gather_into_tensor(gathered, send.contiguous(), group=group)
+        return gathered
+
+    @staticmethod
+    def backward(ctx, dfull):
+        shard = ctx.shard
+        dfull = dfull.contiguous().clone()  # the gloo path reduces in place
+        dx_pad = torch.empty(shard.ag_max_rows, dfull.shape[1],
+                             dtype=dfull.dtype, device=dfull.device)
+        _reduce_scatter(dx_pad, dfull, ctx.group)
+        return dx_pad[:shard.n_local].contiguous(), None, None
+
+
+def _aggregate_reduce(x, shard, reduce, group):
+    """max / min neighbor aggregation of the local block. The exchange
+    completes before the local op starts: there is no comm/compute-overlap
+    variant here (merging partial extrema and their args across the
+    self/remote edge split is a follow-up), whatever ROC_OVERLAP /
+    ROC_AG_OVERLAP say."""
     from ..ops import functional as Fn
+    if shard.world_size == 1:
+        return Fn.scatter_gather_reduce(x, shard, reduce)
+    if shard.comm_mode == "allgather":
+        gathered = _GatherBlocks.apply(x, shard, group)
+        cuda = x.is_cuda
+        return Fn.seg_reduce_csr(
+            gathered, shard.rowptr, shard.ag_colidx, shard.ag_t_rowptr,
+            shard.ag_t_colidx, shard.ag_t_edge_perm32, shard.n_local,
+            shard.world_size * shard.ag_max_rows, reduce,
+            shard.row_order if cuda else None,
+            shard.ag_t_row_order if cuda else None)
+    xe = halo_exchange(x, shard, group)
+    return Fn.scatter_gather_reduce(xe, shard, reduce)
+
+
+def aggregate(x, shard, dst_scale=None, group=None, reduce="sum"):
+    """Distributed neighbor aggregation of the LOCAL feature block.
+    Returns [n_local, D]. reduce="sum" (+ optional fused dst-side degree
+    scale) is the sum / mean path; reduce="max" | "min" takes the
+    elementwise extremum over in-neighbors (first edge wins ties, empty
+    rows give 0; see ops.functional.scatter_gather_reduce) and takes no
+    dst_scale. max / min exchange first and aggregate after, in every
+    comm mode: they have no comm/compute-overlap variant yet."""
+    from ..ops import functional as Fn
+    if reduce != "sum":
+        if dst_scale is not None:
+            raise ValueError("dst_scale applies to reduce='sum' only")
+        return _aggregate_reduce(x, shard, reduce, group)
     if shard.world_size == 1:
         return Fn.scatter_gather(x, shard, dst_scale=dst_scale)
     if shard.comm_mode == "allgather":

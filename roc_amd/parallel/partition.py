@@ -167,6 +167,26 @@ class GraphShard:
             object.__setattr__(self, "_t_eperm", p)
         return p
 
+    def t_edge_perm32(self) -> torch.Tensor:
+        """int32 form of t_edge_perm (the max/min aggregation backward
+        compares it with the int32 winner edge index). Lazily cached."""
+        p = getattr(self, "_t_eperm32", None)
+        if p is None:
+            p = self.t_edge_perm().to(torch.int32)
+            object.__setattr__(self, "_t_eperm32", p)
+        return p
+
+    def ag_t_edge_perm32(self) -> torch.Tensor:
+        """The same map for the allgather-mode gather-space CSR:
+        transposed edge of (ag_t_rowptr, ag_t_colidx) -> forward edge of
+        (rowptr, ag_colidx). Lazily cached."""
+        p = getattr(self, "_ag_t_eperm32", None)
+        if p is None:
+            p = torch.argsort(self.ag_colidx.long(),
+                              stable=True).to(torch.int32)
+            object.__setattr__(self, "_ag_t_eperm32", p)
+        return p
+
 
 def build_strip_plan(rowptr: torch.Tensor, colidx: torch.Tensor,
                      num_cols: int, width: int):

@@ -46,6 +46,9 @@ def parse_args():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
     ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "sgc", "appnp"])
+    ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
+                    help="neighbor aggregation of --model sage: mean, or "
+                         "the elementwise max / min over in-neighbors")
     ap.add_argument("--epochs", "-e", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -139,6 +142,11 @@ def parse_args():
         for k, v in defaults.items():
             if k not in given:
                 setattr(args, k, v)
+    if args.aggr not in ("mean", "max", "min"):  # a YAML value
+        ap.error(f"--aggr must be mean, max or min, got {args.aggr!r}")
+    if args.aggr != "mean" and args.model != "sage":
+        ap.error(f"--aggr {args.aggr} needs --model sage: --model "
+                 f"{args.model} has a fixed aggregation")
     return args
 
 
@@ -231,6 +239,8 @@ def main():
         mkw = {"heads": args.heads}
     elif args.model == "sgc" and args.k_hops:
         mkw = {"k": args.k_hops}
+    elif args.model == "sage":
+        mkw = {"aggr": args.aggr}
     elif args.model == "appnp":
         mkw = {"alpha": args.alpha}
         if args.k_hops:
