@@ -43,6 +43,14 @@ void seg_max_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor arg,
                  torch::Tensor t_rowptr, torch::Tensor t_colidx,
                  torch::Tensor t_eperm,
                  c10::optional<torch::Tensor> t_row_order);
+void layer_norm_fwd(torch::Tensor y, c10::optional<torch::Tensor> mean,
+                    c10::optional<torch::Tensor> rstd, torch::Tensor x,
+                    torch::Tensor gamma, torch::Tensor beta, double eps,
+                    bool relu);
+void layer_norm_bwd(torch::Tensor dx, torch::Tensor dgamma,
+                    torch::Tensor dbeta, torch::Tensor dy, torch::Tensor x,
+                    torch::Tensor mean, torch::Tensor rstd,
+                    torch::Tensor gamma, torch::Tensor beta, bool relu);
 void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
                       torch::Tensor rowptr);
 void edge_softmax_bwd(torch::Tensor ds, torch::Tensor dalpha,
@@ -119,6 +127,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
         pybind11::arg("t_eperm"),
         pybind11::arg("t_row_order") = pybind11::none());
+  m.def("layer_norm_fwd", &layer_norm_fwd,
+        "per-row LayerNorm (+ReLU); mean = rstd = None skips the stats stores",
+        pybind11::arg("y"), pybind11::arg("mean"), pybind11::arg("rstd"),
+        pybind11::arg("x"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("eps"), pybind11::arg("relu") = false);
+  m.def("layer_norm_bwd", &layer_norm_bwd,
+        "LayerNorm gradient: dx, and dgamma / dbeta by an order-fixed slab fold",
+        pybind11::arg("dx"), pybind11::arg("dgamma"), pybind11::arg("dbeta"),
+        pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("mean"),
+        pybind11::arg("rstd"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("relu") = false);
   m.def("edge_softmax_fwd", &edge_softmax_fwd,
         "per-row segment softmax over edge scores (GAT attention)");
   m.def("edge_softmax_bwd", &edge_softmax_bwd);

@@ -3,6 +3,8 @@
 Mirrors the reference driver's model (`gnn.cc:66-92`): per layer
   dropout -> linear -> indegree_norm -> scatter_gather -> indegree_norm
   -> relu (not on last layer) [-> residual projection + add]
+norm="layer" replaces that relu with a fused per-node LayerNorm + ReLU
+(before the residual add); see models/norm.py.
 The two indegree_norms around the aggregation implement the symmetric
 D^-1/2 A D^-1/2 GCN normalization; on GPU they are fused into the SpMM
 kernel (`scatter_gather(..., normalize=True)`).
@@ -17,6 +19,7 @@ from ..ops import functional as F
 from ..ops.reference import glorot_uniform
 from ..parallel.halo import halo_exchange
 from ..parallel.aggregate import aggregate
+from .norm import make_norm_params, hidden_act, norm_parameters
 
 
 def _adaptive_agg() -> bool:
@@ -33,8 +36,10 @@ _ADAPTIVE = None
 
 class GCN(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
-                 residual: bool = False, fused_norm: bool = True):
+                 residual: bool = False, fused_norm: bool = True,
+                 norm: str = "none"):
         super().__init__()
+        self.norm = norm
         self.dims = list(dims)
         self.p = float(dropout)
         self.residual = residual
@@ -49,6 +54,9 @@ class GCN(torch.nn.Module):
                     glorot_uniform((dims[i], dims[i + 1]), seed=seed + 1000 + i)))
             else:
                 self.res_proj.append(torch.nn.Parameter(torch.empty(0)))
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+
+    norm_parameters = norm_parameters
 
     # Activation recompute (capacity tier): when True, each layer's
     # forward is re-run during backward instead of keeping its
@@ -86,7 +94,7 @@ class GCN(torch.nn.Module):
                 F.scatter_gather(F.degree_scale(h, shard.rsqrt_deg_ext), shard),
                 shard)
         if i < len(self.weights) - 1:
-            h = F.relu(h)
+            h = hidden_act(self, i, h)
         if self.residual:
             proj = self.res_proj[i]
             if proj.numel() > 0:

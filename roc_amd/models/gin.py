@@ -2,6 +2,8 @@
 
 h' = MLP( (1 + eps) * h_v + sum_{u in N(v)} h_u ),  eps learnable.
 Exercises the scatter-add aggregation path (BASELINE.json config #4).
+norm="layer" replaces the relu after the MLP's second linear with a fused
+per-node LayerNorm + ReLU on the hidden layers; see models/norm.py.
 """
 from __future__ import annotations
 
@@ -10,12 +12,14 @@ import torch
 from ..ops import functional as F
 from ..ops.reference import glorot_uniform
 from ..parallel.aggregate import aggregate
+from .norm import make_norm_params, hidden_act, norm_parameters
 
 
 class GIN(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
-                 mlp_hidden: int = 0):
+                 mlp_hidden: int = 0, norm: str = "none"):
         super().__init__()
+        self.norm = norm
         self.dims = list(dims)
         self.p = float(dropout)
         self.eps = torch.nn.ParameterList()
@@ -28,6 +32,9 @@ class GIN(torch.nn.Module):
                 glorot_uniform((dims[i], hid), seed=seed + 2 * i)))
             self.w2.append(torch.nn.Parameter(
                 glorot_uniform((hid, dims[i + 1]), seed=seed + 2 * i + 1)))
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+
+    norm_parameters = norm_parameters
 
     recompute = False  # see GCN.recompute
 
@@ -38,7 +45,7 @@ class GIN(torch.nn.Module):
         h = F.linear(h, self.w1[i], activation="relu")
         h = F.linear(h, self.w2[i])
         if i < len(self.w1) - 1:
-            h = F.relu(h)
+            h = hidden_act(self, i, h)
         return h
 
     def forward(self, x, shard, group=None):

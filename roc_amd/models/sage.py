@@ -16,6 +16,10 @@ h' = relu( W_self·h_v  +  W_neigh·ext_{u in N(v)} h_u )
 
 An extremum does not commute with W_neigh, so that layer always
 aggregates first, at the input width, and ROC_ADAPTIVE_AGG does not apply.
+
+norm="layer" replaces the hidden layers' relu with a fused per-node
+LayerNorm + ReLU, on the full-graph and the sampled path alike; see
+models/norm.py.
 """
 from __future__ import annotations
 
@@ -24,12 +28,14 @@ import torch
 from ..ops import functional as F
 from ..ops.reference import glorot_uniform
 from ..parallel.aggregate import aggregate
+from .norm import make_norm_params, hidden_act, norm_parameters
 
 
 class GraphSAGE(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
-                 aggr: str = "mean"):
+                 aggr: str = "mean", norm: str = "none"):
         super().__init__()
+        self.norm = norm
         if aggr not in ("mean", "max", "min"):
             raise ValueError(
                 f"aggr must be 'mean', 'max' or 'min', got {aggr!r}")
@@ -43,6 +49,9 @@ class GraphSAGE(torch.nn.Module):
                 glorot_uniform((dims[i], dims[i + 1]), seed=seed + 2 * i)))
             self.w_neigh.append(torch.nn.Parameter(
                 glorot_uniform((dims[i], dims[i + 1]), seed=seed + 2 * i + 1)))
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+
+    norm_parameters = norm_parameters
 
     def forward(self, x, shard, group=None):
         for i in range(len(self.w_self)):
@@ -77,7 +86,7 @@ class GraphSAGE(torch.nn.Module):
                            group=group)  # fused mean
         h = F.add(h_self, hn)
         if i < len(self.w_self) - 1:
-            h = F.relu(h)
+            h = hidden_act(self, i, h)
         return h
 
     def forward_blocks(self, x, blocks):
@@ -102,5 +111,5 @@ class GraphSAGE(torch.nn.Module):
                 hn = F.scatter_gather(hn, blk, dst_scale=blk.inv_deg)
             x = F.add(h_self, hn)
             if i < len(self.w_self) - 1:
-                x = F.relu(x)
+                x = hidden_act(self, i, x)
         return x

@@ -557,6 +557,94 @@ def degree_scale(x, scale):
 
 
 # ---------------------------------------------------------------------------
+# LayerNorm (+ fused ReLU), per node
+# ---------------------------------------------------------------------------
+
+LAYER_NORM_MAX_D = 1024  # the kernel holds a whole row in registers
+
+
+class _LayerNorm(torch.autograd.Function):
+    """y = act((x - mean) * rstd * gamma + beta) per row (layer_norm.hip).
+    Saves x and the two fp32 [N] row statistics; the backward recomputes
+    x-hat and the relu mask from them, so no [N, D] intermediate is kept.
+    need_stats is False when nothing needs a gradient (decided by the
+    caller: grad mode is always off in here); the kernel variant without
+    the statistics stores runs then. dgamma / dbeta come from an
+    order-fixed slab fold (no atomics, bit-reproducible)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, relu, need_stats):
+        need = need_stats
+        x = x.contiguous()
+        if _hip(x):
+            y = torch.empty_like(x)
+            mean = rstd = None
+            if need:
+                mean = torch.empty(x.shape[0], dtype=torch.float32,
+                                   device=x.device)
+                rstd = torch.empty_like(mean)
+            _C.layer_norm_fwd(y, mean, rstd, x, gamma, beta, eps, relu)
+        else:
+            y, mean, rstd = ref.layer_norm(x, gamma, beta, eps, relu)
+        if need:
+            ctx.save_for_backward(x, mean, rstd, gamma, beta)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, gamma, beta = ctx.saved_tensors
+        dy = dy.contiguous()
+        if _hip(dy):
+            dx = torch.empty_like(x)
+            dgamma = torch.empty_like(gamma)
+            dbeta = torch.empty_like(beta)
+            _C.layer_norm_bwd(dx, dgamma, dbeta, dy, x, mean, rstd, gamma,
+                              beta, ctx.relu)
+        else:
+            dx, dgamma, dbeta = ref.layer_norm_grad(
+                dy, x, mean, rstd, gamma, beta, ctx.relu)
+            dgamma = dgamma.to(gamma.dtype)
+            dbeta = dbeta.to(beta.dtype)
+        return dx, dgamma, dbeta, None, None, None
+
+
+def layer_norm(x, gamma, beta, eps: float = 1e-5,
+               activation: Optional[str] = None):
+    """Per-row LayerNorm over the feature dim with an optional fused ReLU.
+
+    x: [N, D], D <= 1024; bf16 (D % 8 == 0) or fp32 on GPU. gamma, beta:
+    fp32 [D] masters, used as they are (fp64 is accepted next to an fp64
+    x on CPU, for gradcheck). Row-local, so exact at any world size, on
+    sampled blocks and under recompute. Every argument is checked here,
+    before any launch."""
+    if activation not in (None, "relu"):
+        raise ValueError(
+            f"activation must be None or 'relu', got {activation!r}")
+    if x.dim() != 2:
+        raise ValueError(f"x must be [N, D], got {tuple(x.shape)}")
+    D = x.shape[1]
+    if D < 1 or D > LAYER_NORM_MAX_D:
+        raise ValueError(
+            f"layer_norm supports 1 <= D <= {LAYER_NORM_MAX_D}, got D = {D}")
+    if x.is_cuda and x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"layer_norm on GPU takes bf16 or fp32, got {x.dtype}")
+    if x.dtype == torch.bfloat16 and D % 8 != 0:
+        raise ValueError(
+            f"bf16 rows must be a multiple of 8 wide (16 B), got D = {D}")
+    ok = (torch.float32, torch.float64) if x.dtype == torch.float64 \
+        else (torch.float32,)
+    for name, p in (("gamma", gamma), ("beta", beta)):
+        if p.dtype not in ok or tuple(p.shape) != (D,):
+            raise ValueError(
+                f"{name} must be fp32 [{D}], got {p.dtype} {tuple(p.shape)}")
+    need_stats = torch.is_grad_enabled() and (
+        x.requires_grad or gamma.requires_grad or beta.requires_grad)
+    return _LayerNorm.apply(x, gamma.contiguous(), beta.contiguous(),
+                            float(eps), activation == "relu", need_stats)
+
+
+# ---------------------------------------------------------------------------
 # Linear (hand-written MFMA GEMM on GPU)
 # ---------------------------------------------------------------------------
 

@@ -109,6 +109,53 @@ def seg_max_grad(dy: torch.Tensor, arg: torch.Tensor, rowptr: torch.Tensor,
     return dx
 
 
+def _ln_compute_dtype(x: torch.Tensor) -> torch.dtype:
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
+
+
+def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+               eps: float, relu: bool = False):
+    """Per-row LayerNorm (+ ReLU) in the kernel's formula
+    (`csrc/layer_norm.hip`): mean = sum/D, the CENTRED variance
+    sum((x-mean)^2)/D, rstd = 1/sqrt(var+eps),
+    y = act((x-mean)*rstd*gamma + beta). Computed in fp32 (fp64 stays
+    fp64), y cast back to x's dtype. Returns (y, mean [N], rstd [N]);
+    the reference has no normalization layer."""
+    ct = _ln_compute_dtype(x)
+    D = x.shape[1]
+    xf = x.to(ct)
+    mean = xf.sum(dim=1) / D
+    d = xf - mean.unsqueeze(1)
+    var = (d * d).sum(dim=1) / D
+    rstd = 1.0 / torch.sqrt(var + eps)
+    y = d * rstd.unsqueeze(1) * gamma.to(ct) + beta.to(ct)
+    if relu:
+        y = torch.relu(y)
+    return y.to(x.dtype), mean, rstd
+
+
+def layer_norm_grad(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
+                    rstd: torch.Tensor, gamma: torch.Tensor,
+                    beta: torch.Tensor, relu: bool = False):
+    """Gradient of layer_norm from the saved row statistics; xh is
+    recomputed, the relu mask is xh*gamma+beta > 0.
+      dx = rstd * ((g*gamma - mean_j(g*gamma)) - xh * mean_j(g*gamma*xh))
+      dgamma = sum_rows g*xh,  dbeta = sum_rows g
+    Returns (dx in x's dtype, dgamma, dbeta in the compute dtype)."""
+    ct = _ln_compute_dtype(x)
+    D = x.shape[1]
+    gam = gamma.to(ct)
+    xh = (x.to(ct) - mean.unsqueeze(1)) * rstd.unsqueeze(1)
+    g = dy.to(ct)
+    if relu:
+        g = torch.where(xh * gam + beta.to(ct) > 0, g, torch.zeros_like(g))
+    a = g * gam
+    m1 = a.sum(dim=1, keepdim=True) / D
+    m2 = (a * xh).sum(dim=1, keepdim=True) / D
+    dx = rstd.unsqueeze(1) * ((a - m1) - xh * m2)
+    return dx.to(x.dtype), (g * xh).sum(dim=0), g.sum(dim=0)
+
+
 def degnorm(x: torch.Tensor, deg: torch.Tensor) -> torch.Tensor:
     """out[v] = x[v] / sqrt(indeg(v))  (reference `graphnorm_kernel.cu:19-57`)."""
     return x * torch.rsqrt(deg.clamp(min=1.0)).unsqueeze(1).to(x.dtype)

@@ -21,8 +21,13 @@ class AdamOptimizer:
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 0.01,
                  weight_decay: float = 1e-4, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-8,
-                 decay_rate: float = 1.0, decay_steps: int = 100):
+                 decay_rate: float = 1.0, decay_steps: int = 100,
+                 no_decay: Iterable[torch.nn.Parameter] = ()):
         self.params = [p for p in params if p.numel() > 0]
+        # parameters, matched by identity, that take weight_decay = 0: the
+        # coupled L2 term would pull a LayerNorm gamma toward 0
+        self.no_decay = list(no_decay)  # held, so the ids stay theirs
+        self._no_decay = {id(p) for p in self.no_decay}
         self.lr = lr
         self.weight_decay = weight_decay
         self.beta1, self.beta2, self.eps = beta1, beta2, eps
@@ -83,9 +88,9 @@ class AdamOptimizer:
             if self.m[i].device != p.device:  # model moved after ctor
                 self.m[i] = self.m[i].to(p.device)
                 self.v[i] = self.v[i].to(p.device)
+            wd = 0.0 if id(p) in self._no_decay else self.weight_decay
             F.adam_step(p.data, p.grad.data, self.m[i], self.v[i], alpha_t,
-                        self.beta1, self.beta2, self.eps, self.weight_decay,
-                        **step_kw)
+                        self.beta1, self.beta2, self.eps, wd, **step_kw)
         F.bump_weight_version()  # invalidate cached weight casts
 
     def state_dict(self) -> dict:

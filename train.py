@@ -10,7 +10,8 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat, --dtype, --checkpoint/--resume, --trace.
+--model gcn|sage|gin|gat, --norm none|layer, --dtype,
+--checkpoint/--resume, --trace.
 """
 import argparse
 import os
@@ -49,6 +50,9 @@ def parse_args():
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
+    ap.add_argument("--norm", default="none", choices=["none", "layer"],
+                    help="hidden-layer normalization of --model gcn, sage "
+                         "or gin: layer = fused per-node LayerNorm + ReLU")
     ap.add_argument("--epochs", "-e", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -147,6 +151,11 @@ def parse_args():
     if args.aggr != "mean" and args.model != "sage":
         ap.error(f"--aggr {args.aggr} needs --model sage: --model "
                  f"{args.model} has a fixed aggregation")
+    if args.norm not in ("none", "layer"):  # a YAML value
+        ap.error(f"--norm must be none or layer, got {args.norm!r}")
+    if args.norm != "none" and args.model not in ("gcn", "sage", "gin"):
+        ap.error(f"--norm {args.norm} needs --model gcn, sage or gin: "
+                 f"--model {args.model} has no hidden-layer norm")
     return args
 
 
@@ -245,6 +254,8 @@ def main():
         mkw = {"alpha": args.alpha}
         if args.k_hops:
             mkw["k"] = args.k_hops
+    if args.norm != "none":
+        mkw["norm"] = args.norm
     model = build_model(args.model, dims, dropout=args.dropout,
                         seed=args.seed, **mkw)
     if args.recompute:
@@ -254,7 +265,9 @@ def main():
     opt = AdamOptimizer(model.parameters(), lr=args.lr,
                         weight_decay=args.weight_decay,
                         decay_rate=args.decay_rate,
-                        decay_steps=args.decay_steps)
+                        decay_steps=args.decay_steps,
+                        no_decay=model.norm_parameters()
+                        if args.norm != "none" else ())
     dtype = torch.float32
     if args.dtype == "bf16" or (args.dtype == "auto" and on_gpu):
         dtype = torch.bfloat16
