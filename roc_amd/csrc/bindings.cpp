@@ -51,6 +51,23 @@ void layer_norm_bwd(torch::Tensor dx, torch::Tensor dgamma,
                     torch::Tensor dbeta, torch::Tensor dy, torch::Tensor x,
                     torch::Tensor mean, torch::Tensor rstd,
                     torch::Tensor gamma, torch::Tensor beta, bool relu);
+void graph_attn_fwd(torch::Tensor out, c10::optional<torch::Tensor> lse,
+                    torch::Tensor q, torch::Tensor kv, torch::Tensor rowptr,
+                    torch::Tensor colidx,
+                    c10::optional<torch::Tensor> row_order, int64_t heads,
+                    double scale);
+void graph_attn_bwd_dst(torch::Tensor dq, torch::Tensor delta,
+                        torch::Tensor dy, torch::Tensor out, torch::Tensor lse,
+                        torch::Tensor q, torch::Tensor kv,
+                        torch::Tensor rowptr, torch::Tensor colidx,
+                        c10::optional<torch::Tensor> row_order, int64_t heads,
+                        double scale);
+void graph_attn_bwd_src(torch::Tensor dkv, torch::Tensor q, torch::Tensor dy,
+                        torch::Tensor lse, torch::Tensor delta,
+                        torch::Tensor kv, torch::Tensor t_rowptr,
+                        torch::Tensor t_colidx,
+                        c10::optional<torch::Tensor> t_row_order,
+                        int64_t heads, double scale);
 void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
                       torch::Tensor rowptr);
 void edge_softmax_bwd(torch::Tensor ds, torch::Tensor dalpha,
@@ -138,6 +155,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("mean"),
         pybind11::arg("rstd"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("relu") = false);
+  m.def("graph_attn_fwd", &graph_attn_fwd,
+        "dot-product attention over in-neighbours (online softmax); "
+        "lse = None skips the log-sum-exp store",
+        pybind11::arg("out"), pybind11::arg("lse"), pybind11::arg("q"),
+        pybind11::arg("kv"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order"), pybind11::arg("heads"),
+        pybind11::arg("scale"));
+  m.def("graph_attn_bwd_dst", &graph_attn_bwd_dst,
+        "attention gradient, destination-major pass: delta and dq",
+        pybind11::arg("dq"), pybind11::arg("delta"), pybind11::arg("dy"),
+        pybind11::arg("out"), pybind11::arg("lse"), pybind11::arg("q"),
+        pybind11::arg("kv"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order"), pybind11::arg("heads"),
+        pybind11::arg("scale"));
+  m.def("graph_attn_bwd_src", &graph_attn_bwd_src,
+        "attention gradient, source-major pass over the transpose CSR: dkv",
+        pybind11::arg("dkv"), pybind11::arg("q"), pybind11::arg("dy"),
+        pybind11::arg("lse"), pybind11::arg("delta"), pybind11::arg("kv"),
+        pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
+        pybind11::arg("t_row_order"), pybind11::arg("heads"),
+        pybind11::arg("scale"));
   m.def("edge_softmax_fwd", &edge_softmax_fwd,
         "per-row segment softmax over edge scores (GAT attention)");
   m.def("edge_softmax_bwd", &edge_softmax_bwd);

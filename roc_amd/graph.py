@@ -203,7 +203,12 @@ def load_features(path_prefix: str, num_nodes: int, in_dim: int) -> torch.Tensor
     else:
         arr = np.loadtxt(csv_path, delimiter=",", dtype=np.float32)
         arr = np.ascontiguousarray(arr, dtype=np.float32)
-        arr.tofile(bin_path)
+        # every rank of a multi-process run may get here at once, and a
+        # peer reads its window as soon as the cache exists: publish it
+        # whole, by an atomic rename, never half written
+        tmp_path = f"{bin_path}.{os.getpid()}.tmp"
+        arr.tofile(tmp_path)
+        os.replace(tmp_path, bin_path)
     return torch.from_numpy(arr.reshape(num_nodes, in_dim).copy())
 
 

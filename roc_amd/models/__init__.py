@@ -2,6 +2,7 @@ from .gcn import GCN
 from .sage import GraphSAGE
 from .gin import GIN
 from .gat import GAT
+from .transformer import GraphTransformer
 from .sgc import SGC
 from .appnp import APPNP
 
@@ -16,6 +17,8 @@ def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
         return GIN(dims, dropout=dropout, seed=seed, **kw)
     if name == "gat":
         return GAT(dims, dropout=dropout, seed=seed, **kw)
+    if name == "transformer":
+        return GraphTransformer(dims, dropout=dropout, seed=seed, **kw)
     if name == "sgc":
         return SGC(dims, dropout=dropout, seed=seed, **kw)
     if name == "appnp":

@@ -517,6 +517,108 @@ def scatter_gather_reduce(x, shard, reduce: str = "max",
 
 
 # ---------------------------------------------------------------------------
+# Dot-product graph attention (fused online-softmax kernels)
+# ---------------------------------------------------------------------------
+
+class _GraphAttention(torch.autograd.Function):
+    """GPU path of graph_attention (graph_attn.hip). The forward saves
+    out and a fp32 [n, H] log-sum-exp; the backward is two gather passes
+    that recompute p = exp(s - lse): destination-major for delta and dq,
+    source-major over the transpose CSR for dkv. No [E] tensor, no
+    atomics. need_lse is False when nothing needs a gradient (decided by
+    the caller: grad mode is always off in here); the kernel variant
+    without the lse store runs then."""
+
+    @staticmethod
+    def forward(ctx, q, kv, rowptr, colidx, t_rowptr, t_colidx, heads, scale,
+                row_order, t_row_order, need_lse):
+        out = torch.empty_like(q)
+        lse = None
+        if need_lse:
+            lse = torch.empty(q.shape[0], heads, dtype=torch.float32,
+                              device=q.device)
+        _C.graph_attn_fwd(out, lse, q, kv, rowptr, colidx, row_order, heads,
+                          scale)
+        if need_lse:
+            ctx.save_for_backward(q, kv, out, lse, rowptr, colidx, t_rowptr,
+                                  t_colidx, row_order, t_row_order)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (q, kv, out, lse, rowptr, colidx, t_rowptr, t_colidx, row_order,
+         t_row_order) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dq = torch.empty_like(q)
+        delta = torch.empty_like(lse)
+        _C.graph_attn_bwd_dst(dq, delta, dy, out, lse, q, kv, rowptr, colidx,
+                              row_order, ctx.heads, ctx.scale)
+        dkv = None
+        if ctx.needs_input_grad[1]:
+            dkv = torch.empty_like(kv)
+            _C.graph_attn_bwd_src(dkv, q, dy, lse, delta, kv, t_rowptr,
+                                  t_colidx, t_row_order, ctx.heads, ctx.scale)
+        return (dq, dkv) + (None,) * 9
+
+
+def graph_attention_csr(q, kv, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                        num_src, heads, scale=None, row_order=None,
+                        t_row_order=None):
+    """graph_attention over an explicit CSR / transpose-CSR pair. Every
+    argument is checked here, before any launch."""
+    heads = int(heads)
+    if q.dim() != 2 or q.shape[0] != num_rows:
+        raise ValueError(f"q must be [{num_rows}, D], got {tuple(q.shape)}")
+    D = q.shape[1]
+    if heads < 1 or D < heads or D % heads != 0:
+        raise ValueError(
+            f"feature dim {D} is not a positive multiple of {heads} heads")
+    if tuple(kv.shape) != (num_src, 2 * D):
+        # colidx indexes kv unchecked on the GPU: a short kv reads out of
+        # bounds
+        raise ValueError(
+            f"kv must be [{num_src}, {2 * D}], got {tuple(kv.shape)}")
+    if q.dtype != kv.dtype:
+        raise ValueError(
+            f"q and kv must share a dtype, got {q.dtype} and {kv.dtype}")
+    if q.is_cuda and q.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(
+            f"graph_attention on GPU takes bf16 or fp32, got {q.dtype}")
+    if scale is None:
+        scale = float(D // heads) ** -0.5
+    scale = float(scale)
+    if not _hip(q):
+        return ref.graph_attention(q, kv, rowptr, colidx, num_rows, heads,
+                                   scale)
+    need_lse = torch.is_grad_enabled() and (q.requires_grad
+                                            or kv.requires_grad)
+    return _GraphAttention.apply(
+        q.contiguous(), kv.contiguous(), rowptr, colidx, t_rowptr, t_colidx,
+        heads, scale, row_order, t_row_order, need_lse)
+
+
+def graph_attention(q, kv, shard, heads: int, scale: Optional[float] = None):
+    """Scaled dot-product attention over each node's in-neighbourhood
+    (PyG's TransformerConv, the UniMP / graph-transformer family).
+
+    q: [n_local, D], D = heads * dh. kv: [n_ext, 2*D], halo-extended, K
+    in columns [0, D) and V in [D, 2D): one projection GEMM and one halo
+    exchange serve both. For row v, head h and in-edge e from u_e:
+      s_e = scale * <q[v,h,:], K[u_e,h,:]>,  alpha = softmax_e(s),
+      out[v,h,:] = sum_e alpha_e * V[u_e,h,:]
+    scale defaults to dh ** -0.5. Returns [n_local, D] in q's dtype
+    (bf16 or fp32 on GPU; all arithmetic is fp32, one rounding at the
+    store). Duplicate edges each count; a row without edges gives 0 and
+    passes no gradient; a source without out-edges gets a zero gradient.
+    `shard` may be a GraphShard or anything with the same CSR fields."""
+    return graph_attention_csr(
+        q, kv, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+        shard.n_local, shard.n_ext, heads, scale, shard.row_order,
+        shard.t_row_order)
+
+
+# ---------------------------------------------------------------------------
 # InDegreeNorm
 # ---------------------------------------------------------------------------
 

@@ -109,6 +109,41 @@ def seg_max_grad(dy: torch.Tensor, arg: torch.Tensor, rowptr: torch.Tensor,
     return dx
 
 
+def graph_attention(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
+                    colidx: torch.Tensor, num_rows: int, heads: int,
+                    scale: float) -> torch.Tensor:
+    """Scaled dot-product attention over the in-neighbourhood (PyG's
+    TransformerConv without its extras; the reference has no attention):
+      s_e = scale * <q[v,h,:], K[u_e,h,:]>   for the edges e of row v
+      out[v,h,:] = sum_e softmax_e(s) * V[u_e,h,:]
+    q: [num_rows, D], D = heads * dh; kv: [n_src, 2*D] with K in columns
+    [0, D) and V in [D, 2D). Duplicate edges each count; a row without
+    edges gives 0. Max-subtracted softmax out of index ops, in fp32 (fp64
+    stays fp64), differentiable by autograd; the result is cast back to
+    q's dtype."""
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    D = q.shape[1]
+    dh = D // heads
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=q.device), deg)
+    src = colidx.to(torch.long)
+    E = int(src.numel())
+    qh = q.to(ct).view(num_rows, heads, dh)
+    kvh = kv.to(ct).view(kv.shape[0], 2, heads, dh)
+    s = (qh[dst] * kvh[src, 0]).sum(dim=2) * scale               # [E, H]
+    m = torch.zeros(num_rows, heads, dtype=ct, device=q.device)
+    m = m.scatter_reduce(0, dst.unsqueeze(1).expand(E, heads), s.detach(),
+                         reduce="amax", include_self=False)
+    ex = (s - m[dst]).exp()
+    den = torch.zeros(num_rows, heads, dtype=ct,
+                      device=q.device).index_add(0, dst, ex)
+    alpha = ex / den[dst]
+    out = torch.zeros(num_rows, heads, dh, dtype=ct, device=q.device)
+    out = out.index_add(0, dst, alpha.unsqueeze(2) * kvh[src, 1])
+    return out.reshape(num_rows, D).to(q.dtype)
+
+
 def _ln_compute_dtype(x: torch.Tensor) -> torch.dtype:
     return torch.float64 if x.dtype == torch.float64 else torch.float32
 

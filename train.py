@@ -10,7 +10,7 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat, --norm none|layer, --dtype,
+--model gcn|sage|gin|gat|transformer, --norm none|layer, --dtype,
 --checkpoint/--resume, --trace.
 """
 import argparse
@@ -46,13 +46,15 @@ def parse_args():
                          "e.g. 602-256-41")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
-    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "sgc", "appnp"])
+    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "transformer", "sgc",
+                             "appnp"])
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
     ap.add_argument("--norm", default="none", choices=["none", "layer"],
-                    help="hidden-layer normalization of --model gcn, sage "
-                         "or gin: layer = fused per-node LayerNorm + ReLU")
+                    help="hidden-layer normalization of --model gcn, sage, "
+                         "gin or transformer: layer = fused per-node "
+                         "LayerNorm + ReLU")
     ap.add_argument("--epochs", "-e", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -66,7 +68,8 @@ def parse_args():
     ap.add_argument("--eval-every", type=int, default=5)
     ap.add_argument("--residual", action="store_true")
     ap.add_argument("--heads", type=int, default=4,
-                    help="GAT attention heads (concat; last layer 1)")
+                    help="attention heads of --model gat or transformer "
+                         "(concat; last layer 1)")
     ap.add_argument("--k-hops", type=int, default=None,
                     help="SGC propagation depth (default 2) / APPNP "
                          "propagation steps (default 10)")
@@ -153,9 +156,11 @@ def parse_args():
                  f"{args.model} has a fixed aggregation")
     if args.norm not in ("none", "layer"):  # a YAML value
         ap.error(f"--norm must be none or layer, got {args.norm!r}")
-    if args.norm != "none" and args.model not in ("gcn", "sage", "gin"):
-        ap.error(f"--norm {args.norm} needs --model gcn, sage or gin: "
-                 f"--model {args.model} has no hidden-layer norm")
+    if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
+                                                  "transformer"):
+        ap.error(f"--norm {args.norm} needs --model gcn, sage, gin or "
+                 f"transformer: --model {args.model} has no hidden-layer "
+                 f"norm")
     return args
 
 
@@ -244,7 +249,7 @@ def main():
         shard = build_shard(g, rank, world, bounds,
                             use_comm=(world > 1 and dist.is_initialized()))
     mkw = {"residual": args.residual} if args.model == "gcn" else {}
-    if args.model == "gat":
+    if args.model in ("gat", "transformer"):
         mkw = {"heads": args.heads}
     elif args.model == "sgc" and args.k_hops:
         mkw = {"k": args.k_hops}
