@@ -35,8 +35,7 @@
 // The fast path needs dh % EPU == 0 and dh <= 64 * EPU. Any other dh >= 1
 // runs the lane-strided scalar kernels at the end of this file.
 
-#include <climits>
-
+#include "csr_launch.h"
 #include "gather.h"
 
 namespace {
@@ -46,16 +45,6 @@ namespace {
 // resource table).
 constexpr int kDepth = 8;
 constexpr int kColdTeam = 8;
-
-__device__ __forceinline__ void unpack(float* v, const uint4& r) {
-  v[0] = bf16_lo(r.x); v[1] = bf16_hi(r.x);
-  v[2] = bf16_lo(r.y); v[3] = bf16_hi(r.y);
-  v[4] = bf16_lo(r.z); v[5] = bf16_hi(r.z);
-  v[6] = bf16_lo(r.w); v[7] = bf16_hi(r.w);
-}
-__device__ __forceinline__ void unpack(float* v, const float4& r) {
-  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-}
 
 // the lane's partial of a head dot product, a fixed fma chain
 template <int EPU>
@@ -76,28 +65,9 @@ __device__ __forceinline__ void load_unit(float* v, const T* p, bool active) {
   }
 }
 
-// Two gather engines over one matrix (K and V halves of kv) or over two
-// matrices of one shape (q and dy), at the lane's column offsets.
-template <typename T, bool BUF>
-struct Engine;
-template <typename T>
-struct Engine<T, true> {
-  using type = BufferGather<T>;
-  static __device__ __forceinline__ type make(const T* x, unsigned bytes,
-                                              int64_t ld, int64_t col0) {
-    return type{__builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, bytes,
-                                                  0x00020000),
-                (unsigned)(ld * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-  }
-};
-template <typename T>
-struct Engine<T, false> {
-  using type = GlobalGather<T>;
-  static __device__ __forceinline__ type make(const T* x, unsigned,
-                                              int64_t ld, int64_t col0) {
-    return type{x, ld, col0};
-  }
-};
+// Every kernel below makes two gather engines (gather.h): over one matrix
+// (the K and V halves of kv) or over two matrices of one shape (q and dy),
+// at the lane's column offsets.
 
 // ---------------------------------------------------------------------------
 // forward
@@ -163,8 +133,8 @@ __global__ __launch_bounds__(kBlock) void graph_attn_fwd_kernel(
   const int64_t D = (int64_t)heads * dh;
   const bool active = rt.lane * EPU < dh;
   const int64_t col = (int64_t)h * dh + (active ? rt.lane * EPU : 0);
-  const auto ldk = Engine<T, BUF>::make(kv, kv_bytes, 2 * D, col);
-  const auto ldv = Engine<T, BUF>::make(kv, kv_bytes, 2 * D, D + col);
+  const auto ldk = make_gather<T, BUF>(kv, kv_bytes, 2 * D, col);
+  const auto ldv = make_gather<T, BUF>(kv, kv_bytes, 2 * D, D + col);
 
   for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
     const int row = row_order ? row_order[ri] : ri;
@@ -175,12 +145,9 @@ __global__ __launch_bounds__(kBlock) void graph_attn_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < EPU; ++j) acc[j] = 0.f;
     Softmax st{0.f, 0.f, true};
-    for (; e + kDepth - 1 < e1; e += kDepth)
-      fwd_group<kDepth, T, TEAM>(st, acc, qf, scale, ldk, ldv, colidx, e);
-    for (; e + 3 < e1; e += 4)
-      fwd_group<4, T, TEAM>(st, acc, qf, scale, ldk, ldv, colidx, e);
-    for (; e < e1; ++e)
-      fwd_group<1, T, TEAM>(st, acc, qf, scale, ldk, ldv, colidx, e);
+    ROC_EDGE_LADDER(kDepth, e, e1,
+                    fwd_group<ROC_LADDER_N, T, TEAM>(st, acc, qf, scale, ldk,
+                                                     ldv, colidx, e));
     // an empty row keeps l = 0 and acc = 0: out = 0, lse = 0
     const float inv = st.first ? 0.f : 1.f / st.l;
 #pragma unroll
@@ -238,8 +205,8 @@ __global__ __launch_bounds__(kBlock) void graph_attn_bwd_dst_kernel(
   const int64_t D = (int64_t)heads * dh;
   const bool active = rt.lane * EPU < dh;
   const int64_t col = (int64_t)h * dh + (active ? rt.lane * EPU : 0);
-  const auto ldk = Engine<T, BUF>::make(kv, kv_bytes, 2 * D, col);
-  const auto ldv = Engine<T, BUF>::make(kv, kv_bytes, 2 * D, D + col);
+  const auto ldk = make_gather<T, BUF>(kv, kv_bytes, 2 * D, col);
+  const auto ldv = make_gather<T, BUF>(kv, kv_bytes, 2 * D, D + col);
 
   for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
     const int row = row_order ? row_order[ri] : ri;
@@ -255,13 +222,9 @@ __global__ __launch_bounds__(kBlock) void graph_attn_bwd_dst_kernel(
     if (rt.lane == 0) delta[(int64_t)row * heads + h] = dl;
 #pragma unroll
     for (int j = 0; j < EPU; ++j) acc[j] = 0.f;
-    for (; e + kDepth - 1 < e1; e += kDepth)
-      dst_group<kDepth, T, TEAM>(acc, qf, gf, scale, ls, dl, ldk, ldv, colidx,
-                                 e);
-    for (; e + 3 < e1; e += 4)
-      dst_group<4, T, TEAM>(acc, qf, gf, scale, ls, dl, ldk, ldv, colidx, e);
-    for (; e < e1; ++e)
-      dst_group<1, T, TEAM>(acc, qf, gf, scale, ls, dl, ldk, ldv, colidx, e);
+    ROC_EDGE_LADDER(kDepth, e, e1,
+                    dst_group<ROC_LADDER_N, T, TEAM>(acc, qf, gf, scale, ls, dl,
+                                                     ldk, ldv, colidx, e));
 #pragma unroll
     for (int j = 0; j < EPU; ++j) acc[j] *= scale;
     if (active) store_vec(dq + at, acc);  // the one rounding
@@ -324,8 +287,8 @@ __global__ __launch_bounds__(kBlock) void graph_attn_bwd_src_kernel(
   const int64_t D = (int64_t)heads * dh;
   const bool active = rt.lane * EPU < dh;
   const int64_t col = (int64_t)h * dh + (active ? rt.lane * EPU : 0);
-  const auto ldq = Engine<T, BUF>::make(q, q_bytes, D, col);
-  const auto ldg = Engine<T, BUF>::make(dy, q_bytes, D, col);
+  const auto ldq = make_gather<T, BUF>(q, q_bytes, D, col);
+  const auto ldg = make_gather<T, BUF>(dy, q_bytes, D, col);
 
   for (int ri = rt.team; ri < num_src; ri += rt.nteams) {
     const int u = t_row_order ? t_row_order[ri] : ri;
@@ -337,15 +300,10 @@ __global__ __launch_bounds__(kBlock) void graph_attn_bwd_src_kernel(
     load_unit(vf, kv + at + D, active);
 #pragma unroll
     for (int j = 0; j < EPU; ++j) dk[j] = dv[j] = 0.f;
-    for (; k + kDepth - 1 < k1; k += kDepth)
-      src_group<kDepth, T, TEAM>(dk, dv, kf, vf, scale, lse, delta, heads, h,
-                                 ldq, ldg, t_colidx, k);
-    for (; k + 3 < k1; k += 4)
-      src_group<4, T, TEAM>(dk, dv, kf, vf, scale, lse, delta, heads, h, ldq,
-                            ldg, t_colidx, k);
-    for (; k < k1; ++k)
-      src_group<1, T, TEAM>(dk, dv, kf, vf, scale, lse, delta, heads, h, ldq,
-                            ldg, t_colidx, k);
+    ROC_EDGE_LADDER(
+        kDepth, k, k1,
+        src_group<ROC_LADDER_N, T, TEAM>(dk, dv, kf, vf, scale, lse, delta,
+                                         heads, h, ldq, ldg, t_colidx, k));
 #pragma unroll
     for (int j = 0; j < EPU; ++j) dk[j] *= scale;
     if (active) {
@@ -486,37 +444,26 @@ __global__ __launch_bounds__(kBlock) void graph_attn_bwd_src_cold_kernel(
 // launchers
 // ---------------------------------------------------------------------------
 
+// The frame's geometry with a head per column tile, and whether the fast
+// kernels serve this dh (the cold ones run teams of kColdTeam, in natural
+// row order).
 struct AttnGeom {
   bool fast;
-  int team;
-  dim3 grid;
-  bool buf;
-  unsigned bytes;
+  GatherGeom g;
 };
 
 template <typename T>
 AttnGeom attn_geom(int num_rows, int heads, int dh, size_t gathered_elems) {
   constexpr int EPU = EltTraits<T>::kPerVec;
-  AttnGeom g;
-  g.fast = dh % EPU == 0 && dh <= 64 * EPU;
-  g.team = g.fast ? row_team_size(dh / EPU) : kColdTeam;
-  g.grid = row_team_grid(num_rows, g.team, heads);
-  const size_t b = gathered_elems * sizeof(T);
-  g.buf = b < (size_t)UINT_MAX;
-  g.bytes = (unsigned)(g.buf ? b : 0);
-  return g;
+  const bool fast = dh % EPU == 0 && dh <= 64 * EPU;
+  return {fast, gather_geom<T>(num_rows, dh / EPU, heads, gathered_elems, true,
+                               fast ? 0 : kColdTeam)};
 }
 
-void check_csr(const torch::Tensor& rowptr, const torch::Tensor& colidx,
-               int64_t num_rows, const char* what) {
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, what,
-              ": rowptr must be int64");
-  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, what,
-              ": colidx must be int32");
-  TORCH_CHECK(rowptr.dim() == 1 && rowptr.size(0) == num_rows + 1, what,
-              ": rowptr size mismatch");
+const int* attn_order(const c10::optional<torch::Tensor>& order, int64_t n,
+                      const AttnGeom& a, const char* what) {
+  const int* p = row_order_ptr(order, n, a.g.team, what);
+  return a.fast ? p : nullptr;
 }
 
 void check_rowstat(const torch::Tensor& t, int64_t n, int64_t heads,
@@ -530,36 +477,16 @@ void check_rowstat(const torch::Tensor& t, int64_t n, int64_t heads,
 // q-shaped [n, D] against kv-shaped [n_ext, 2D]; returns dh
 int check_qkv(const torch::Tensor& q, const torch::Tensor& kv, int64_t heads,
               const char* what) {
-  ROC_CHECK_DEV_CONT(q);
-  ROC_CHECK_DEV_CONT(kv);
-  TORCH_CHECK(q.dim() == 2 && kv.dim() == 2, what, ": 2-D tensors");
+  check_mat(q, what, "q");
+  check_mat(kv, what, "kv");
   TORCH_CHECK(q.scalar_type() == kv.scalar_type(), what,
               ": q and kv must share a dtype");
-  TORCH_CHECK(q.size(0) < INT_MAX && kv.size(0) < INT_MAX, what,
-              ": too many rows");
   const int64_t D = q.size(1);
   TORCH_CHECK(kv.size(1) == 2 * D, what, ": kv must be [n_ext, 2*D]");
   TORCH_CHECK(heads >= 1 && heads <= 65535 && D >= heads && D % heads == 0,
               what, ": D must be a positive multiple of heads (<= 65535)");
   TORCH_CHECK(D < INT_MAX / 8, what, ": feature dim too large");
   return (int)(D / heads);
-}
-
-void check_like(const torch::Tensor& t, const torch::Tensor& ref,
-                const char* what, const char* name) {
-  ROC_CHECK_DEV_CONT(t);
-  TORCH_CHECK(t.scalar_type() == ref.scalar_type() && t.sizes() == ref.sizes(),
-              what, ": ", name, " must have the shape and dtype of its input");
-}
-
-const int* attn_order(const c10::optional<torch::Tensor>& order, int64_t n,
-                      const AttnGeom& g) {
-  if (!order.has_value()) return nullptr;
-  ROC_CHECK_DEV_CONT(*order);
-  TORCH_CHECK(order->scalar_type() == torch::kInt32 && order->numel() == n,
-              "row_order must be int32 [num_rows]");
-  // same cut-off as spmm and seg_max: the indirection pays for wide rows
-  return (!g.fast || g.team < 16) ? nullptr : order->data_ptr<int>();
 }
 
 }  // namespace
@@ -587,30 +514,28 @@ void graph_attn_fwd(torch::Tensor out, c10::optional<torch::Tensor> lse,
   auto stream = roc_stream();
   dispatch_elt(q.scalar_type(), "graph_attn_fwd", [&](auto xt) {
     using T = typename decltype(xt)::type;
-    const AttnGeom g =
+    const AttnGeom a =
         attn_geom<T>(num_rows, (int)heads, dh, (size_t)kv.numel());
-    const int* order = attn_order(row_order, num_rows, g);
+    const int* order = attn_order(row_order, num_rows, a, "graph_attn_fwd");
     dispatch_bool(lsep != nullptr, [&](auto lse_c) {
-      if (!g.fast) {
+      if (!a.fast) {
         hipLaunchKernelGGL(
-            (graph_attn_fwd_cold_kernel<T, decltype(lse_c)::value>), g.grid,
+            (graph_attn_fwd_cold_kernel<T, decltype(lse_c)::value>), a.g.grid,
             dim3(kBlock), 0, stream, (T*)out.data_ptr(), lsep,
             (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
             rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), num_rows,
             (int)heads, dh, (float)scale);
         return;
       }
-      dispatch_team(g.team, [&](auto team_c) {
-        dispatch_bool(g.buf, [&](auto buf_c) {
-          hipLaunchKernelGGL(
-              (graph_attn_fwd_kernel<T, decltype(team_c)::value,
-                                     decltype(buf_c)::value,
-                                     decltype(lse_c)::value>),
-              g.grid, dim3(kBlock), 0, stream, (T*)out.data_ptr(), lsep,
-              (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
-              rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), order,
-              num_rows, (int)heads, dh, (float)scale, g.bytes);
-        });
+      dispatch_gather(a.g, [&](auto team_c, auto buf_c) {
+        hipLaunchKernelGGL(
+            (graph_attn_fwd_kernel<T, decltype(team_c)::value,
+                                   decltype(buf_c)::value,
+                                   decltype(lse_c)::value>),
+            a.g.grid, dim3(kBlock), 0, stream, (T*)out.data_ptr(), lsep,
+            (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
+            rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), order,
+            num_rows, (int)heads, dh, (float)scale, a.g.bytes);
       });
     });
   });
@@ -640,12 +565,13 @@ void graph_attn_bwd_dst(torch::Tensor dq, torch::Tensor delta,
   auto stream = roc_stream();
   dispatch_elt(q.scalar_type(), "graph_attn_bwd_dst", [&](auto xt) {
     using T = typename decltype(xt)::type;
-    const AttnGeom g =
+    const AttnGeom a =
         attn_geom<T>(num_rows, (int)heads, dh, (size_t)kv.numel());
-    const int* order = attn_order(row_order, num_rows, g);
-    if (!g.fast) {
+    const int* order =
+        attn_order(row_order, num_rows, a, "graph_attn_bwd_dst");
+    if (!a.fast) {
       hipLaunchKernelGGL(
-          (graph_attn_bwd_dst_cold_kernel<T>), g.grid, dim3(kBlock), 0, stream,
+          (graph_attn_bwd_dst_cold_kernel<T>), a.g.grid, dim3(kBlock), 0, stream,
           (T*)dq.data_ptr(), delta.data_ptr<float>(), (const T*)dy.data_ptr(),
           (const T*)out.data_ptr(), lse.data_ptr<float>(),
           (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
@@ -653,18 +579,16 @@ void graph_attn_bwd_dst(torch::Tensor dq, torch::Tensor delta,
           (int)heads, dh, (float)scale);
       return;
     }
-    dispatch_team(g.team, [&](auto team_c) {
-      dispatch_bool(g.buf, [&](auto buf_c) {
-        hipLaunchKernelGGL(
-            (graph_attn_bwd_dst_kernel<T, decltype(team_c)::value,
-                                       decltype(buf_c)::value>),
-            g.grid, dim3(kBlock), 0, stream, (T*)dq.data_ptr(),
-            delta.data_ptr<float>(), (const T*)dy.data_ptr(),
-            (const T*)out.data_ptr(), lse.data_ptr<float>(),
-            (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
-            rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), order,
-            num_rows, (int)heads, dh, (float)scale, g.bytes);
-      });
+    dispatch_gather(a.g, [&](auto team_c, auto buf_c) {
+      hipLaunchKernelGGL(
+          (graph_attn_bwd_dst_kernel<T, decltype(team_c)::value,
+                                     decltype(buf_c)::value>),
+          a.g.grid, dim3(kBlock), 0, stream, (T*)dq.data_ptr(),
+          delta.data_ptr<float>(), (const T*)dy.data_ptr(),
+          (const T*)out.data_ptr(), lse.data_ptr<float>(),
+          (const T*)q.data_ptr(), (const T*)kv.data_ptr(),
+          rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(), order, num_rows,
+          (int)heads, dh, (float)scale, a.g.bytes);
     });
   });
   ROC_HIP_CHECK(hipGetLastError());
@@ -692,30 +616,29 @@ void graph_attn_bwd_src(torch::Tensor dkv, torch::Tensor q, torch::Tensor dy,
   auto stream = roc_stream();
   dispatch_elt(q.scalar_type(), "graph_attn_bwd_src", [&](auto xt) {
     using T = typename decltype(xt)::type;
-    const AttnGeom g =
+    // the src pass gathers rows of q and dy, so the buffer spans q
+    const AttnGeom a =
         attn_geom<T>(num_src, (int)heads, dh, (size_t)q.numel());
-    const int* order = attn_order(t_row_order, num_src, g);
-    if (!g.fast) {
+    const int* order = attn_order(t_row_order, num_src, a, "graph_attn_bwd_src");
+    if (!a.fast) {
       hipLaunchKernelGGL(
-          (graph_attn_bwd_src_cold_kernel<T>), g.grid, dim3(kBlock), 0, stream,
+          (graph_attn_bwd_src_cold_kernel<T>), a.g.grid, dim3(kBlock), 0, stream,
           (T*)dkv.data_ptr(), (const T*)q.data_ptr(), (const T*)dy.data_ptr(),
           lse.data_ptr<float>(), delta.data_ptr<float>(),
           (const T*)kv.data_ptr(), t_rowptr.data_ptr<int64_t>(),
           t_colidx.data_ptr<int>(), num_src, (int)heads, dh, (float)scale);
       return;
     }
-    dispatch_team(g.team, [&](auto team_c) {
-      dispatch_bool(g.buf, [&](auto buf_c) {
-        hipLaunchKernelGGL(
-            (graph_attn_bwd_src_kernel<T, decltype(team_c)::value,
-                                       decltype(buf_c)::value>),
-            g.grid, dim3(kBlock), 0, stream, (T*)dkv.data_ptr(),
-            (const T*)q.data_ptr(), (const T*)dy.data_ptr(),
-            lse.data_ptr<float>(), delta.data_ptr<float>(),
-            (const T*)kv.data_ptr(), t_rowptr.data_ptr<int64_t>(),
-            t_colidx.data_ptr<int>(), order, num_src, (int)heads, dh,
-            (float)scale, g.bytes);
-      });
+    dispatch_gather(a.g, [&](auto team_c, auto buf_c) {
+      hipLaunchKernelGGL(
+          (graph_attn_bwd_src_kernel<T, decltype(team_c)::value,
+                                     decltype(buf_c)::value>),
+          a.g.grid, dim3(kBlock), 0, stream, (T*)dkv.data_ptr(),
+          (const T*)q.data_ptr(), (const T*)dy.data_ptr(),
+          lse.data_ptr<float>(), delta.data_ptr<float>(),
+          (const T*)kv.data_ptr(), t_rowptr.data_ptr<int64_t>(),
+          t_colidx.data_ptr<int>(), order, num_src, (int)heads, dh,
+          (float)scale, a.g.bytes);
     });
   });
   ROC_HIP_CHECK(hipGetLastError());

@@ -1,5 +1,7 @@
 // Row-team frame shared by the CSR kernels (spmm.hip, seg_max.hip,
-// edge_softmax.hip).
+// graph_attn.hip, edge_softmax.hip) and by the row kernels of
+// layer_norm.hip. gather.h adds the device side of the feature-row
+// gathers, csr_launch.h the host side of their launches.
 //
 // A team of TEAM contiguous lanes (a power of two <= 64, so a team never
 // straddles a wave64) owns one CSR row at a time; teams grid-stride over

@@ -25,8 +25,7 @@
 //    source id would make the backward count the winner once per duplicate
 // NaN inputs are out of contract.
 
-#include <climits>
-
+#include "csr_launch.h"
 #include "gather.h"
 
 namespace {
@@ -37,16 +36,6 @@ namespace {
 // by 9% at the Reddit shape, without scratch (profiles/r39).
 constexpr int kFwdDepth = 16;
 constexpr int kBwdDepth = 16;
-
-__device__ __forceinline__ void unpack(float* v, const uint4& r) {
-  v[0] = bf16_lo(r.x); v[1] = bf16_hi(r.x);
-  v[2] = bf16_lo(r.y); v[3] = bf16_hi(r.y);
-  v[4] = bf16_lo(r.z); v[5] = bf16_hi(r.z);
-  v[6] = bf16_lo(r.w); v[7] = bf16_hi(r.w);
-}
-__device__ __forceinline__ void unpack(float* v, const float4& r) {
-  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-}
 
 template <bool MIN>
 __device__ __forceinline__ bool beats(float v, float best) {
@@ -77,15 +66,9 @@ template <typename T, int UN, bool MIN, bool ARG, typename LD>
 __device__ __forceinline__ void row_ext_vec(
     float* __restrict__ best, int* __restrict__ barg, const LD& ld,
     const int* __restrict__ colidx, int64_t e, int64_t e1) {
-  if constexpr (UN >= 16)
-    for (; e + 15 < e1; e += 16)
-      ext_group<16, T, MIN, ARG>(best, barg, ld, colidx, e);
-  if constexpr (UN >= 8)
-    for (; e + 7 < e1; e += 8)
-      ext_group<8, T, MIN, ARG>(best, barg, ld, colidx, e);
-  for (; e + 3 < e1; e += 4)
-    ext_group<4, T, MIN, ARG>(best, barg, ld, colidx, e);
-  for (; e < e1; ++e) ext_group<1, T, MIN, ARG>(best, barg, ld, colidx, e);
+  ROC_EDGE_LADDER(
+      UN, e, e1,
+      ext_group<ROC_LADDER_N, T, MIN, ARG>(best, barg, ld, colidx, e));
 }
 
 template <int EPU>
@@ -139,18 +122,9 @@ __global__ __launch_bounds__(kBlock) void seg_max_fwd_kernel(
   const int nvalid = full ? EPU : (col0 < D ? (int)(D - col0) : 0);
 
   if (full) {
-    if constexpr (BUF) {
-      const BufferGather<T> g{
-          __builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, x_bytes,
-                                            0x00020000),
-          (unsigned)(D * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-      fwd_rows_vec<T, UN, MIN, ARG>(rt, g, out, arg, rowptr, colidx, row_order,
-                                    num_rows, D, col0);
-    } else {
-      const GlobalGather<T> g{x, D, col0};
-      fwd_rows_vec<T, UN, MIN, ARG>(rt, g, out, arg, rowptr, colidx, row_order,
-                                    num_rows, D, col0);
-    }
+    const auto g = make_gather<T, BUF>(x, x_bytes, D, col0);
+    fwd_rows_vec<T, UN, MIN, ARG>(rt, g, out, arg, rowptr, colidx, row_order,
+                                  num_rows, D, col0);
   } else if (nvalid > 0) {
     // cold path: the unit straddles D (D % EPU != 0). One column at a time,
     // scalar loads, the running best in two scalars.
@@ -233,16 +207,9 @@ __device__ __forceinline__ void bwd_rows_vec(
     float acc[EPU];
 #pragma unroll
     for (int j = 0; j < EPU; ++j) acc[j] = 0.f;
-    if constexpr (UN >= 16)
-      for (; k + 15 < k1; k += 16)
-        route_group<16, T>(acc, g, arg, D, col0, t_colidx, t_eperm, k);
-    if constexpr (UN >= 8)
-      for (; k + 7 < k1; k += 8)
-        route_group<8, T>(acc, g, arg, D, col0, t_colidx, t_eperm, k);
-    for (; k + 3 < k1; k += 4)
-      route_group<4, T>(acc, g, arg, D, col0, t_colidx, t_eperm, k);
-    for (; k < k1; ++k)
-      route_group<1, T>(acc, g, arg, D, col0, t_colidx, t_eperm, k);
+    ROC_EDGE_LADDER(UN, k, k1,
+                    route_group<ROC_LADDER_N, T>(acc, g, arg, D, col0, t_colidx,
+                                                 t_eperm, k));
     store_vec(dx + (int64_t)u * D + col0, acc);  // the one rounding
   }
 }
@@ -260,18 +227,9 @@ __global__ __launch_bounds__(kBlock) void seg_max_bwd_kernel(
   const int nvalid = full ? EPU : (col0 < D ? (int)(D - col0) : 0);
 
   if (full) {
-    if constexpr (BUF) {
-      const BufferGather<T> g{
-          __builtin_amdgcn_make_buffer_rsrc((void*)dy, (short)0, dy_bytes,
-                                            0x00020000),
-          (unsigned)(D * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-      bwd_rows_vec<T, UN>(rt, g, dx, arg, t_rowptr, t_colidx, t_eperm,
-                          t_row_order, num_src, D, col0);
-    } else {
-      const GlobalGather<T> g{dy, D, col0};
-      bwd_rows_vec<T, UN>(rt, g, dx, arg, t_rowptr, t_colidx, t_eperm,
-                          t_row_order, num_src, D, col0);
-    }
+    const auto g = make_gather<T, BUF>(dy, dy_bytes, D, col0);
+    bwd_rows_vec<T, UN>(rt, g, dx, arg, t_rowptr, t_colidx, t_eperm,
+                        t_row_order, num_src, D, col0);
   } else if (nvalid > 0) {
     // cold path: one column at a time, scalar loads
     for (int ri = rt.team; ri < num_src; ri += rt.nteams) {
@@ -290,49 +248,18 @@ __global__ __launch_bounds__(kBlock) void seg_max_bwd_kernel(
   }
 }
 
-// geometry of one launch: team by width, column tiles, gather engine by size
-struct SegGeom {
-  int team;
-  dim3 grid;
-  bool buf;
-  unsigned bytes;
-};
-
-template <typename T>
-SegGeom seg_geom(int num_rows, int64_t D, size_t gathered_elems) {
-  constexpr int EPU = EltTraits<T>::kPerVec;
-  const int64_t units = (D + EPU - 1) / EPU;
-  SegGeom g;
-  g.team = row_team_size(units);
-  g.grid = row_team_grid(num_rows, g.team, (int)((units + g.team - 1) / g.team));
-  const size_t b = gathered_elems * sizeof(T);
-  g.buf = b < (size_t)UINT_MAX;
-  g.bytes = (unsigned)(g.buf ? b : 0);
-  return g;
-}
-
+// arg and t_eperm carry edge indices as int32
 void check_csr_i32(const torch::Tensor& rowptr, const torch::Tensor& colidx,
                    int64_t num_rows, const char* what) {
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, what,
-              ": rowptr must be int64");
-  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, what,
-              ": colidx must be int32");
-  TORCH_CHECK(rowptr.size(0) == num_rows + 1, what, ": rowptr size mismatch");
-  // arg and t_eperm carry edge indices as int32
+  check_csr(rowptr, colidx, num_rows, what);
   TORCH_CHECK(colidx.numel() < ((int64_t)1 << 31), what,
               ": 2^31 or more edges do not fit the int32 edge index");
 }
 
-const int* order_ptr(const c10::optional<torch::Tensor>& order, int64_t n,
-                     int team) {
-  if (!order.has_value()) return nullptr;
-  ROC_CHECK_DEV_CONT(*order);
-  TORCH_CHECK(order->scalar_type() == torch::kInt32 && order->numel() == n,
-              "row_order must be int32 [num_rows]");
-  // same cut-off as spmm: the indirection only pays for wide rows
-  return team < 16 ? nullptr : order->data_ptr<int>();
+template <typename T>
+GatherGeom seg_geom(int num_rows, int64_t D, size_t gathered_elems) {
+  constexpr int EPU = EltTraits<T>::kPerVec;
+  return gather_geom<T>(num_rows, (D + EPU - 1) / EPU, 0, gathered_elems);
 }
 
 }  // namespace
@@ -340,16 +267,11 @@ const int* order_ptr(const c10::optional<torch::Tensor>& order, int64_t n,
 void seg_max_fwd(torch::Tensor out, c10::optional<torch::Tensor> arg,
                  torch::Tensor x, torch::Tensor rowptr, torch::Tensor colidx,
                  c10::optional<torch::Tensor> row_order, bool is_min) {
-  ROC_CHECK_DEV_CONT(out);
-  ROC_CHECK_DEV_CONT(x);
-  TORCH_CHECK(out.dim() == 2 && x.dim() == 2, "seg_max_fwd: 2-D tensors");
+  check_mat_pair(out, "out", x, "x", "seg_max_fwd");
   TORCH_CHECK(out.scalar_type() == x.scalar_type(),
               "seg_max_fwd: out and x must share a dtype");
-  TORCH_CHECK(out.size(0) < INT_MAX && x.size(0) < INT_MAX,
-              "seg_max_fwd: too many rows");
   const int num_rows = (int)out.size(0);
   const int64_t D = out.size(1);
-  TORCH_CHECK(x.size(1) == D, "seg_max_fwd: feature dim mismatch");
   check_csr_i32(rowptr, colidx, num_rows, "seg_max_fwd");
   int* argp = nullptr;
   if (arg.has_value()) {
@@ -363,21 +285,19 @@ void seg_max_fwd(torch::Tensor out, c10::optional<torch::Tensor> arg,
   auto stream = roc_stream();
   dispatch_elt(x.scalar_type(), "seg_max_fwd", [&](auto xt) {
     using T = typename decltype(xt)::type;
-    const SegGeom g = seg_geom<T>(num_rows, D, (size_t)x.numel());
-    const int* order = order_ptr(row_order, num_rows, g.team);
-    dispatch_team(g.team, [&](auto team_c) {
-      dispatch_bool(g.buf, [&](auto buf_c) {
-        dispatch_bool(is_min, [&](auto min_c) {
-          dispatch_bool(argp != nullptr, [&](auto arg_c) {
-            hipLaunchKernelGGL(
-                (seg_max_fwd_kernel<T, decltype(team_c)::value, kFwdDepth,
-                                    decltype(buf_c)::value,
-                                    decltype(min_c)::value,
-                                    decltype(arg_c)::value>),
-                g.grid, dim3(kBlock), 0, stream, (T*)out.data_ptr(), argp,
-                (const T*)x.data_ptr(), rowptr.data_ptr<int64_t>(),
-                colidx.data_ptr<int>(), order, num_rows, D, g.bytes);
-          });
+    const GatherGeom g = seg_geom<T>(num_rows, D, (size_t)x.numel());
+    const int* order = row_order_ptr(row_order, num_rows, g.team, "seg_max_fwd");
+    dispatch_gather(g, [&](auto team_c, auto buf_c) {
+      dispatch_bool(is_min, [&](auto min_c) {
+        dispatch_bool(argp != nullptr, [&](auto arg_c) {
+          hipLaunchKernelGGL(
+              (seg_max_fwd_kernel<T, decltype(team_c)::value, kFwdDepth,
+                                  decltype(buf_c)::value,
+                                  decltype(min_c)::value,
+                                  decltype(arg_c)::value>),
+              g.grid, dim3(kBlock), 0, stream, (T*)out.data_ptr(), argp,
+              (const T*)x.data_ptr(), rowptr.data_ptr<int64_t>(),
+              colidx.data_ptr<int>(), order, num_rows, D, g.bytes);
         });
       });
     });
@@ -389,18 +309,13 @@ void seg_max_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor arg,
                  torch::Tensor t_rowptr, torch::Tensor t_colidx,
                  torch::Tensor t_eperm,
                  c10::optional<torch::Tensor> t_row_order) {
-  ROC_CHECK_DEV_CONT(dx);
-  ROC_CHECK_DEV_CONT(dy);
+  check_mat_pair(dx, "dx", dy, "dy", "seg_max_bwd");
   ROC_CHECK_DEV_CONT(arg);
   ROC_CHECK_DEV_CONT(t_eperm);
-  TORCH_CHECK(dx.dim() == 2 && dy.dim() == 2, "seg_max_bwd: 2-D tensors");
   TORCH_CHECK(dx.scalar_type() == dy.scalar_type(),
               "seg_max_bwd: dx and dy must share a dtype");
-  TORCH_CHECK(dx.size(0) < INT_MAX && dy.size(0) < INT_MAX,
-              "seg_max_bwd: too many rows");
   const int num_src = (int)dx.size(0);
   const int64_t D = dx.size(1);
-  TORCH_CHECK(dy.size(1) == D, "seg_max_bwd: feature dim mismatch");
   TORCH_CHECK(arg.scalar_type() == torch::kInt32 && arg.sizes() == dy.sizes(),
               "seg_max_bwd: arg must be int32 with the shape of dy");
   check_csr_i32(t_rowptr, t_colidx, num_src, "seg_max_bwd");
@@ -411,18 +326,16 @@ void seg_max_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor arg,
   auto stream = roc_stream();
   dispatch_elt(dy.scalar_type(), "seg_max_bwd", [&](auto xt) {
     using T = typename decltype(xt)::type;
-    const SegGeom g = seg_geom<T>(num_src, D, (size_t)dy.numel());
-    const int* order = order_ptr(t_row_order, num_src, g.team);
-    dispatch_team(g.team, [&](auto team_c) {
-      dispatch_bool(g.buf, [&](auto buf_c) {
-        hipLaunchKernelGGL(
-            (seg_max_bwd_kernel<T, decltype(team_c)::value, kBwdDepth,
-                                decltype(buf_c)::value>),
-            g.grid, dim3(kBlock), 0, stream, (T*)dx.data_ptr(),
-            (const T*)dy.data_ptr(), arg.data_ptr<int>(),
-            t_rowptr.data_ptr<int64_t>(), t_colidx.data_ptr<int>(),
-            t_eperm.data_ptr<int>(), order, num_src, D, g.bytes);
-      });
+    const GatherGeom g = seg_geom<T>(num_src, D, (size_t)dy.numel());
+    const int* order = row_order_ptr(t_row_order, num_src, g.team, "seg_max_bwd");
+    dispatch_gather(g, [&](auto team_c, auto buf_c) {
+      hipLaunchKernelGGL(
+          (seg_max_bwd_kernel<T, decltype(team_c)::value, kBwdDepth,
+                              decltype(buf_c)::value>),
+          g.grid, dim3(kBlock), 0, stream, (T*)dx.data_ptr(),
+          (const T*)dy.data_ptr(), arg.data_ptr<int>(),
+          t_rowptr.data_ptr<int64_t>(), t_colidx.data_ptr<int>(),
+          t_eperm.data_ptr<int>(), order, num_src, D, g.bytes);
     });
   });
   ROC_HIP_CHECK(hipGetLastError());

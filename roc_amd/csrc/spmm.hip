@@ -29,6 +29,7 @@
 // Backward runs this same kernel on the transpose CSR (exact on
 // asymmetric graphs; the reference assumed symmetry).
 
+#include "csr_launch.h"
 #include "gather.h"
 
 namespace {
@@ -76,12 +77,9 @@ template <typename T, int UN, Weight W, typename LD>
 __device__ __forceinline__ void row_accum_vec(
     float* __restrict__ acc, const LD& ld, const int* __restrict__ colidx,
     const float* __restrict__ weight, int64_t e, int64_t e1) {
-  if constexpr (UN >= 16)
-    for (; e + 15 < e1; e += 16) accum_group<16, T, W>(acc, ld, colidx, weight, e);
-  if constexpr (UN >= 8)
-    for (; e + 7 < e1; e += 8) accum_group<8, T, W>(acc, ld, colidx, weight, e);
-  for (; e + 3 < e1; e += 4) accum_group<4, T, W>(acc, ld, colidx, weight, e);
-  for (; e < e1; ++e) accum_group<1, T, W>(acc, ld, colidx, weight, e);
+  ROC_EDGE_LADDER(
+      UN, e, e1,
+      accum_group<ROC_LADDER_N, T, W>(acc, ld, colidx, weight, e));
 }
 
 // tail path: unit straddles the column window (only when its width is
@@ -169,16 +167,8 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] = 0.f;
       }
-      if constexpr (BUF) {
-        BufferGather<T> g{
-            __builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, x_bytes,
-                                              0x00020000),
-            (unsigned)(ld * sizeof(T)), (unsigned)(col0 * sizeof(T))};
-        row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
-      } else {
-        GlobalGather<T> g{x, ld, col0};
-        row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
-      }
+      const auto g = make_gather<T, BUF>(x, x_bytes, ld, col0);
+      row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
       if (deg_dst) {
         const float s = deg_dst[row];
 #pragma unroll
@@ -270,8 +260,8 @@ static const SpmmKnobs& spmm_knobs() {
 }
 
 // The one spmm_kernel launch: geometry from the column window, gather
-// engine from the matrix size, TEAM and BUF lifted to template constants.
-// team_override == 0 picks the team by width.
+// engine from the matrix size (csr_launch.h). team_override == 0 picks the
+// team by width; `what` names the op in the row_order message.
 // The strip-pass extras of one launch (see spmm_kernel): the heavy-first
 // list with its threshold, and the bf16 destination of a final pass.
 struct StripPass {
@@ -286,31 +276,23 @@ template <typename T, typename OT, int UN, Weight W, bool HEAVY = false,
           bool FINAL = false>
 void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
                  const int* colidx, const float* deg_dst, const float* weight,
-                 const int* row_order, int num_rows, int64_t ld,
-                 int64_t col_base, int64_t col_end, bool accumulate,
-                 size_t x_elems, int team_override, hipStream_t stream,
+                 const c10::optional<torch::Tensor>& row_order, int num_rows,
+                 int64_t ld, int64_t col_base, int64_t col_end,
+                 bool accumulate, size_t x_elems, int team_override,
+                 const char* what, hipStream_t stream,
                  const StripPass& sp = {}) {
   constexpr int EPU = EltTraits<T>::kPerVec;
-  const int64_t units = (col_end - col_base + EPU - 1) / EPU;
-  const int team = team_override ? team_override : row_team_size(units);
-  const dim3 grid =
-      row_team_grid(num_rows, team, (int)((units + team - 1) / team));
-  const size_t xb = x_elems * sizeof(T);
-  const bool buf = xb < (size_t)UINT_MAX && spmm_knobs().allow_buffer;
-  const unsigned x_bytes = (unsigned)(buf ? xb : 0);
-  // measured (scripts/bench_spmm.py, Reddit shape): degree-descending
-  // scheduling wins for wide rows (D=256: -13%) but loses for narrow
-  // ones (D=48: +10% — the indirection costs more than the skew tail)
-  if (team < 16) row_order = nullptr;
-  dispatch_team(team, [&](auto team_c) {
-    dispatch_bool(buf, [&](auto buf_c) {
-      hipLaunchKernelGGL(
-          (spmm_kernel<T, OT, decltype(team_c)::value, UN,
-                       decltype(buf_c)::value, W, HEAVY, FINAL>),
-          grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
-          weight, row_order, num_rows, ld, col_base, col_end, accumulate,
-          x_bytes, sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out);
-    });
+  const GatherGeom g = gather_geom<T>(
+      num_rows, (col_end - col_base + EPU - 1) / EPU, 0, x_elems,
+      spmm_knobs().allow_buffer, team_override);
+  const int* order = row_order_ptr(row_order, num_rows, g.team, what);
+  dispatch_gather(g, [&](auto team_c, auto buf_c) {
+    hipLaunchKernelGGL(
+        (spmm_kernel<T, OT, decltype(team_c)::value, UN,
+                     decltype(buf_c)::value, W, HEAVY, FINAL>),
+        g.grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
+        weight, order, num_rows, ld, col_base, col_end, accumulate, g.bytes,
+        sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out);
   });
 }
 
@@ -373,10 +355,9 @@ __global__ __launch_bounds__(kBlock) void edge_dot_kernel(
       float a[EPU] = {0.f};
       if (live) acc_add(a, load_raw(dy + (int64_t)row * D + g.col0), 1.f);
       int64_t e = e0;
-      for (; e + 3 < e1; e += 4)
-        edge_dot_group<4, T, TEAM>(dw, a, g, colidx, e, live, lane);
-      for (; e < e1; ++e)
-        edge_dot_group<1, T, TEAM>(dw, a, g, colidx, e, live, lane);
+      ROC_EDGE_LADDER(4, e, e1,
+                      edge_dot_group<ROC_LADDER_N, T, TEAM>(dw, a, g, colidx, e,
+                                                            live, lane));
     }
     return;
   }
@@ -419,15 +400,6 @@ void launch_edge_dot(float* dw, const T* dy, const T* x,
   });
 }
 
-void check_csr(const torch::Tensor& rowptr, const torch::Tensor& colidx,
-               int num_rows) {
-  ROC_CHECK_DEV_CONT(rowptr);
-  ROC_CHECK_DEV_CONT(colidx);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64, "rowptr must be int64");
-  TORCH_CHECK(colidx.scalar_type() == torch::kInt32, "colidx must be int32");
-  TORCH_CHECK(rowptr.size(0) == num_rows + 1, "rowptr size mismatch");
-}
-
 template <typename T>
 const T* opt_ptr(const c10::optional<torch::Tensor>& t) {
   return t.has_value() ? t->data_ptr<T>() : nullptr;
@@ -446,24 +418,24 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           int64_t col_base, int64_t ncols,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
           c10::optional<torch::Tensor> final_out) {
-  ROC_CHECK_DEV_CONT(out);
-  ROC_CHECK_DEV_CONT(x);
+  check_mat_pair(out, "out", x, "x", "spmm");
   // strip-pass extras: heavy-first schedule and fused final bf16 store
   StripPass sp;
   if (heavy_rows.has_value() || final_out.has_value()) {
     TORCH_CHECK(out.scalar_type() == torch::kFloat32 &&
                     x.scalar_type() == torch::kBFloat16 &&
                     !deg_src.has_value(),
-                "heavy_rows / final_out are strip-pass options: bf16 x, "
-                "fp32 out, no deg_src");
+                "spmm: heavy_rows / final_out are strip-pass options: "
+                "bf16 x, fp32 out, no deg_src");
   }
   if (heavy_rows.has_value()) {
     ROC_CHECK_DEV_CONT(*heavy_rows);
     TORCH_CHECK(heavy_rows->scalar_type() == torch::kInt32,
-                "heavy_rows must be int32");
+                "spmm: heavy_rows must be int32");
     TORCH_CHECK(!row_order.has_value(),
-                "heavy_rows and row_order are exclusive");
-    TORCH_CHECK(heavy_min >= 0 && heavy_min <= INT_MAX, "bad heavy_min");
+                "spmm: heavy_rows and row_order are exclusive");
+    TORCH_CHECK(heavy_min >= 0 && heavy_min <= INT_MAX,
+                "spmm: bad heavy_min");
     sp.heavy = true;
     sp.heavy_rows = heavy_rows->data_ptr<int>();
     sp.num_heavy = (int)heavy_rows->numel();
@@ -472,26 +444,25 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
   if (final_out.has_value()) {
     ROC_CHECK_DEV_CONT(*final_out);
     TORCH_CHECK(final_out->scalar_type() == torch::kBFloat16,
-                "final_out must be bf16");
+                "spmm: final_out must be bf16");
     TORCH_CHECK(final_out->sizes() == out.sizes(),
-                "final_out shape mismatch");
+                "spmm: final_out shape mismatch");
     TORCH_CHECK(col_base == 0 && ncols == 0,
-                "final_out needs a whole-row pass");
+                "spmm: final_out needs a whole-row pass");
     sp.final_out = (unsigned short*)final_out->data_ptr();
   }
   TORCH_CHECK(out.scalar_type() == x.scalar_type() ||
                   (out.scalar_type() == torch::kFloat32 &&
                    x.scalar_type() == torch::kBFloat16),
-              "dtype mismatch (out must match x, or be fp32 for bf16 x)");
+              "spmm: dtype mismatch (out must match x, or be fp32 for bf16 x)");
   const int num_rows = (int)out.size(0);
   const int64_t D = out.size(1);
-  TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  check_csr(rowptr, colidx, num_rows);
+  check_csr(rowptr, colidx, num_rows, "spmm");
   // column-phase pass: touch only [col_base, col_base+ncols) of every
   // row (ncols == 0 -> the whole row). The stride stays D.
   const int64_t col_end = ncols > 0 ? col_base + ncols : D;
   TORCH_CHECK(col_base >= 0 && col_base < col_end && col_end <= D,
-              "bad column window");
+              "spmm: bad column window");
   const float* ds = opt_ptr<float>(deg_src);
   const SpmmKnobs& kn = spmm_knobs();
   auto stream = roc_stream();
@@ -509,9 +480,9 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
                         decltype(final_c)::value>(
                 (OT*)out.data_ptr(), (const T*)x.data_ptr(),
                 rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
-                opt_ptr<float>(deg_dst), ds, opt_ptr<int>(row_order),
-                num_rows, D, col_base, col_end, accumulate,
-                (size_t)x.numel(), kn.team_override, stream, sp);
+                opt_ptr<float>(deg_dst), ds, row_order, num_rows, D,
+                col_base, col_end, accumulate, (size_t)x.numel(),
+                kn.team_override, "spmm", stream, sp);
           };
           // the strip-pass variants exist for bf16 -> fp32, no weight only
           // (checked above), so nothing else is instantiated with them
@@ -548,26 +519,26 @@ void spmm_edge(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
                torch::Tensor colidx, torch::Tensor edge_val,
                c10::optional<torch::Tensor> deg_dst,
                c10::optional<torch::Tensor> row_order, bool accumulate) {
-  ROC_CHECK_DEV_CONT(out);
-  ROC_CHECK_DEV_CONT(x);
+  check_mat_pair(out, "out", x, "x", "spmm_edge");
   ROC_CHECK_DEV_CONT(edge_val);
   TORCH_CHECK(edge_val.scalar_type() == torch::kFloat32,
-              "edge_val must be fp32");
-  TORCH_CHECK(edge_val.numel() == colidx.numel(), "edge_val size mismatch");
-  TORCH_CHECK(out.scalar_type() == x.scalar_type(), "dtype mismatch");
+              "spmm_edge: edge_val must be fp32");
+  TORCH_CHECK(edge_val.numel() == colidx.numel(),
+              "spmm_edge: edge_val size mismatch");
+  TORCH_CHECK(out.scalar_type() == x.scalar_type(),
+              "spmm_edge: dtype mismatch");
   const int num_rows = (int)out.size(0);
   const int64_t D = out.size(1);
-  TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  check_csr(rowptr, colidx, num_rows);
+  check_csr(rowptr, colidx, num_rows, "spmm_edge");
   auto stream = roc_stream();
   dispatch_elt(x.scalar_type(), "spmm_edge", [&](auto xt) {
     using T = typename decltype(xt)::type;
     launch_spmm<T, T, 4, Weight::kEdge>(
         (T*)out.data_ptr(), (const T*)x.data_ptr(),
         rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
-        opt_ptr<float>(deg_dst), edge_val.data_ptr<float>(),
-        opt_ptr<int>(row_order), num_rows, D, 0, D, accumulate,
-        (size_t)x.numel(), 0, stream);
+        opt_ptr<float>(deg_dst), edge_val.data_ptr<float>(), row_order,
+        num_rows, D, 0, D, accumulate, (size_t)x.numel(), 0, "spmm_edge",
+        stream);
   });
   ROC_HIP_CHECK(hipGetLastError());
 }
@@ -575,15 +546,13 @@ void spmm_edge(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
 void edge_dot(torch::Tensor dw, torch::Tensor dy, torch::Tensor x,
               torch::Tensor rowptr, torch::Tensor colidx) {
   ROC_CHECK_DEV_CONT(dw);
-  ROC_CHECK_DEV_CONT(dy);
-  ROC_CHECK_DEV_CONT(x);
-  TORCH_CHECK(dw.scalar_type() == torch::kFloat32, "dw must be fp32");
-  TORCH_CHECK(dw.numel() == colidx.numel(), "dw size mismatch");
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type(), "dtype mismatch");
+  check_mat_pair(dy, "dy", x, "x", "edge_dot");
+  TORCH_CHECK(dw.scalar_type() == torch::kFloat32, "edge_dot: dw must be fp32");
+  TORCH_CHECK(dw.numel() == colidx.numel(), "edge_dot: dw size mismatch");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type(), "edge_dot: dtype mismatch");
   const int num_rows = (int)dy.size(0);
   const int64_t D = dy.size(1);
-  TORCH_CHECK(x.size(1) == D, "feature dim mismatch");
-  check_csr(rowptr, colidx, num_rows);
+  check_csr(rowptr, colidx, num_rows, "edge_dot");
   auto stream = roc_stream();
   dispatch_elt(dy.scalar_type(), "edge_dot", [&](auto xt) {
     using T = typename decltype(xt)::type;
