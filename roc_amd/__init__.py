@@ -21,4 +21,4 @@ from .parallel.partition import (GraphShard, build_shard,  # noqa: F401
 from .optim import AdamOptimizer  # noqa: F401
 from .engine import Trainer  # noqa: F401
 from .models import (build_model, GCN, GraphSAGE, GIN, GAT,  # noqa: F401
-                     GraphTransformer)
+                     GraphTransformer, PNA, pna_delta)

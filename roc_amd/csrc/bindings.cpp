@@ -43,6 +43,16 @@ void seg_max_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor arg,
                  torch::Tensor t_rowptr, torch::Tensor t_colidx,
                  torch::Tensor t_eperm,
                  c10::optional<torch::Tensor> t_row_order);
+void seg_stats_fwd(torch::Tensor out, c10::optional<torch::Tensor> stats,
+                   c10::optional<torch::Tensor> arg, torch::Tensor x,
+                   torch::Tensor rowptr, torch::Tensor colidx,
+                   c10::optional<torch::Tensor> row_order, double eps,
+                   int64_t depth);
+void seg_stats_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor x,
+                   torch::Tensor stats, torch::Tensor arg,
+                   torch::Tensor rowptr, torch::Tensor t_rowptr,
+                   torch::Tensor t_colidx, torch::Tensor t_eperm,
+                   c10::optional<torch::Tensor> t_row_order, int64_t depth);
 void layer_norm_fwd(torch::Tensor y, c10::optional<torch::Tensor> mean,
                     c10::optional<torch::Tensor> rstd, torch::Tensor x,
                     torch::Tensor gamma, torch::Tensor beta, double eps,
@@ -144,6 +154,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
         pybind11::arg("t_eperm"),
         pybind11::arg("t_row_order") = pybind11::none());
+  m.def("seg_stats_fwd", &seg_stats_fwd,
+        "CSR segment mean/std/max/min in one gather: out = [mean|std|max|min],"
+        " stats = fp32 [mean|1/std], arg = [argmax|argmin] forward edges; "
+        "stats = arg = None skips their stores",
+        pybind11::arg("out"), pybind11::arg("stats"), pybind11::arg("arg"),
+        pybind11::arg("x"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order") = pybind11::none(),
+        pybind11::arg("eps") = 1e-5, pybind11::arg("depth") = 0);
+  m.def("seg_stats_bwd", &seg_stats_bwd,
+        "seg_stats gradient: one gather of stats, dy and arg over the "
+        "transpose CSR",
+        pybind11::arg("dx"), pybind11::arg("dy"), pybind11::arg("x"),
+        pybind11::arg("stats"), pybind11::arg("arg"),
+        pybind11::arg("rowptr"), pybind11::arg("t_rowptr"),
+        pybind11::arg("t_colidx"),
+        pybind11::arg("t_eperm"),
+        pybind11::arg("t_row_order") = pybind11::none(),
+        pybind11::arg("depth") = 0);
   m.def("layer_norm_fwd", &layer_norm_fwd,
         "per-row LayerNorm (+ReLU); mean = rstd = None skips the stats stores",
         pybind11::arg("y"), pybind11::arg("mean"), pybind11::arg("rstd"),

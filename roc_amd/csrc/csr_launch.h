@@ -1,5 +1,5 @@
 // Host side of the row-team CSR gather frame (spmm.hip, seg_max.hip,
-// graph_attn.hip): argument checks, launch geometry, and the lift of
+// seg_stats.hip, graph_attn.hip): argument checks, launch geometry, and the lift of
 // (team, gather engine) to template constants. docs/KERNELS.md, "The
 // row-team gather frame", describes the whole frame.
 #pragma once
@@ -19,6 +19,16 @@ inline void check_csr(const torch::Tensor& rowptr, const torch::Tensor& colidx,
               ": colidx must be int32");
   TORCH_CHECK(rowptr.dim() == 1 && rowptr.size(0) == num_rows + 1, what,
               ": rowptr size mismatch");
+}
+
+// for the ops whose arg and t_eperm carry edge indices as int32
+// (seg_max.hip, seg_stats.hip)
+inline void check_csr_i32(const torch::Tensor& rowptr,
+                          const torch::Tensor& colidx, int64_t num_rows,
+                          const char* what) {
+  check_csr(rowptr, colidx, num_rows, what);
+  TORCH_CHECK(colidx.numel() < ((int64_t)1 << 31), what,
+              ": 2^31 or more edges do not fit the int32 edge index");
 }
 
 // a feature matrix: 2-D, and its row count fits the kernels' int

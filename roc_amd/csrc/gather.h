@@ -1,5 +1,6 @@
 // 16-B row-gather helpers shared by the row-team CSR kernels that read
-// feature rows through colidx (spmm.hip, seg_max.hip, graph_attn.hip):
+// feature rows through colidx (spmm.hip, seg_max.hip, seg_stats.hip,
+// graph_attn.hip):
 // the raw payload and its widen, the two gather engines and their
 // factory, one rung of the unroll ladder and the ladder itself.
 #pragma once
@@ -31,6 +32,15 @@ __device__ __forceinline__ void unpack(float* v, const uint4& r) {
 }
 __device__ __forceinline__ void unpack(float* v, const float4& r) {
   v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+}
+
+// one unit of winner edge indices (seg_max.hip, seg_stats.hip)
+template <int EPU>
+__device__ __forceinline__ void store_arg(int* p, const int (&a)[EPU]) {
+#pragma unroll
+  for (int q = 0; q < EPU; q += 4)
+    *reinterpret_cast<int4*>(p + q) =
+        make_int4(a[q], a[q + 1], a[q + 2], a[q + 3]);
 }
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;

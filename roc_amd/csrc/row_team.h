@@ -1,5 +1,5 @@
 // Row-team frame shared by the CSR kernels (spmm.hip, seg_max.hip,
-// graph_attn.hip, edge_softmax.hip) and by the row kernels of
+// seg_stats.hip, graph_attn.hip, edge_softmax.hip) and by the row kernels of
 // layer_norm.hip. gather.h adds the device side of the feature-row
 // gathers, csr_launch.h the host side of their launches.
 //

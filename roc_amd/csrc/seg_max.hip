@@ -71,14 +71,6 @@ __device__ __forceinline__ void row_ext_vec(
       ext_group<ROC_LADDER_N, T, MIN, ARG>(best, barg, ld, colidx, e));
 }
 
-template <int EPU>
-__device__ __forceinline__ void store_arg(int* p, const int (&a)[EPU]) {
-#pragma unroll
-  for (int q = 0; q < EPU; q += 4)
-    *reinterpret_cast<int4*>(p + q) =
-        make_int4(a[q], a[q + 1], a[q + 2], a[q + 3]);
-}
-
 // hot path of the forward: every row this team owns, one full unit per lane
 template <typename T, int UN, bool MIN, bool ARG, typename TEAM_T, typename LD>
 __device__ __forceinline__ void fwd_rows_vec(
@@ -246,14 +238,6 @@ __global__ __launch_bounds__(kBlock) void seg_max_bwd_kernel(
       }
     }
   }
-}
-
-// arg and t_eperm carry edge indices as int32
-void check_csr_i32(const torch::Tensor& rowptr, const torch::Tensor& colidx,
-                   int64_t num_rows, const char* what) {
-  check_csr(rowptr, colidx, num_rows, what);
-  TORCH_CHECK(colidx.numel() < ((int64_t)1 << 31), what,
-              ": 2^31 or more edges do not fit the int32 edge index");
 }
 
 template <typename T>

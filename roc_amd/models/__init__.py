@@ -5,6 +5,7 @@ from .gat import GAT
 from .transformer import GraphTransformer
 from .sgc import SGC
 from .appnp import APPNP
+from .pna import PNA, pna_delta
 
 
 def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
@@ -23,4 +24,6 @@ def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
         return SGC(dims, dropout=dropout, seed=seed, **kw)
     if name == "appnp":
         return APPNP(dims, dropout=dropout, seed=seed, **kw)
+    if name == "pna":
+        return PNA(dims, dropout=dropout, seed=seed, **kw)
     raise ValueError(f"unknown model {name!r}")

@@ -506,14 +506,100 @@ def scatter_gather_reduce(x, shard, reduce: str = "max",
     edge index of each winner (-1 on empty rows). `shard` may be a
     GraphShard or a sampling Block; a Block has no cached edge
     permutation, so its backward map is computed per call."""
+    return seg_reduce_csr(
+        x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+        _edge_perm_thunk(shard), shard.n_local, shard.n_ext, reduce,
+        shard.row_order, shard.t_row_order, return_arg)
+
+
+class _SegStats(torch.autograd.Function):
+    """out[v] = [mean | std | max | min] over in-neighbors of x[u], all four
+    from one gather of each neighbor row (seg_stats.hip). When x needs a
+    gradient the forward also saves stats (fp32 [mean | 1/std], so the
+    backward never sees the rounded out) and arg (the winning forward edges
+    of max and min). The backward is one deterministic gather over the
+    transpose CSR — no atomics. t_eperm is a thunk, called only when a
+    gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, t_eperm,
+                num_rows, num_src, eps, row_order, t_row_order):
+        need_grad = ctx.needs_input_grad[0]
+        x = x.contiguous()
+        if _hip(x):
+            D = x.shape[1]
+            out = torch.empty(num_rows, 4 * D, dtype=x.dtype, device=x.device)
+            stats = arg = None
+            if need_grad:
+                stats = torch.empty(num_rows, 2 * D, dtype=torch.float32,
+                                    device=x.device)
+                arg = torch.empty(num_rows, 2 * D, dtype=torch.int32,
+                                  device=x.device)
+            _C.seg_stats_fwd(out, stats, arg, x, rowptr, colidx, row_order,
+                             eps)
+        else:
+            out, stats, arg = ref.seg_stats(x, rowptr, colidx, num_rows, eps)
+        ctx.num_src = num_src
+        if need_grad:
+            if x.is_cuda:
+                ctx.save_for_backward(x, stats, arg, rowptr, t_rowptr,
+                                      t_colidx, t_eperm(), t_row_order)
+            else:
+                ctx.save_for_backward(x, stats, arg, rowptr, colidx)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        if _hip(dy):
+            (x, stats, arg, rowptr, t_rowptr, t_colidx, t_eperm,
+             t_row_order) = ctx.saved_tensors
+            dx = torch.empty_like(x)
+            _C.seg_stats_bwd(dx, dy, x, stats, arg, rowptr, t_rowptr,
+                             t_colidx, t_eperm, t_row_order)
+        else:
+            x, stats, arg, rowptr, colidx = ctx.saved_tensors
+            dx = ref.seg_stats_grad(dy, x, stats, arg, rowptr, colidx,
+                                    ctx.num_src)
+        return (dx,) + (None,) * 10
+
+
+def seg_stats_csr(x, rowptr, colidx, t_rowptr, t_colidx, t_eperm, num_rows,
+                  num_src, eps=1e-5, row_order=None, t_row_order=None):
+    """scatter_gather_stats over an explicit CSR / transpose-CSR pair.
+    t_eperm: a callable returning the int32 [E] map from transposed edge
+    to forward edge (the stable argsort of colidx)."""
+    if x.dim() != 2 or x.shape[0] != num_src:
+        # colidx indexes x unchecked on the GPU: a short x reads out of bounds
+        raise ValueError(f"x must be [{num_src}, D], got {tuple(x.shape)}")
+    return _SegStats.apply(x, rowptr, colidx, t_rowptr, t_colidx, t_eperm,
+                           num_rows, num_src, float(eps), row_order,
+                           t_row_order)
+
+
+def _edge_perm_thunk(shard):
+    """The shard's cached int32 transposed-edge -> forward-edge map; a
+    sampling Block has none, so its map is computed per call."""
     cached = getattr(shard, "t_edge_perm32", None)
     if cached is None:
         def cached():
             return torch.argsort(shard.colidx.long(), stable=True).int()
-    return seg_reduce_csr(
+    return cached
+
+
+def scatter_gather_stats(x, shard, eps: float = 1e-5):
+    """The four PNA aggregators over the shard's local CSR in one pass.
+
+    x: [n_ext, D] halo-extended features. Returns [n_local, 4*D] in x's
+    dtype, laid out [mean | std | max | min]: std = sqrt(var + eps) with
+    the population variance, max / min as scatter_gather_reduce gives them
+    (bit for bit an input, first edge wins ties and takes the whole
+    gradient). Rows without edges give 0 and pass no gradient. `shard` may
+    be a GraphShard or a sampling Block."""
+    return seg_stats_csr(
         x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
-        cached, shard.n_local, shard.n_ext, reduce, shard.row_order,
-        shard.t_row_order, return_arg)
+        _edge_perm_thunk(shard), shard.n_local, shard.n_ext, eps,
+        shard.row_order, shard.t_row_order)
 
 
 # ---------------------------------------------------------------------------

@@ -109,6 +109,77 @@ def seg_max_grad(dy: torch.Tensor, arg: torch.Tensor, rowptr: torch.Tensor,
     return dx
 
 
+def seg_stats(x: torch.Tensor, rowptr: torch.Tensor, colidx: torch.Tensor,
+              num_rows: int, eps: float = 1e-5):
+    """The four PNA aggregators of every row's in-neighbourhood.
+    Returns (out, stats, arg):
+      out   [num_rows, 4*D] = [mean | std | max | min], in x's dtype
+      stats [num_rows, 2*D] = [mean | 1/std], unrounded (fp32; fp64 stays)
+      arg   [num_rows, 2*D] = [argmax | argmin], int32 forward edge indices
+    std = sqrt(var + eps) with the POPULATION variance, computed in two
+    passes (the mean first, then the centred squares) on values shifted by
+    the row's first edge, so degree-1 rows and rows of equal values have
+    var == 0 exactly. max / min and their args are seg_max's (first edge
+    wins ties). An empty row gives 0 everywhere and arg -1. NaN and +-inf
+    inputs are out of contract."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    D = x.shape[1]
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=x.device), deg)
+    empty = (deg == 0).unsqueeze(1)
+    degc = deg.clamp(min=1).to(ct).unsqueeze(1)
+    xc = x.to(ct)
+    E = int(colidx.numel())
+    zeros = torch.zeros(num_rows, D, dtype=ct, device=x.device)
+    if E == 0:
+        mean, std, rstd = zeros, zeros, zeros
+    else:
+        src = colidx.to(torch.long)
+        # a trailing empty row starts at E: clamped, then masked
+        first = src[rowptr[:-1].to(torch.long).clamp(max=E - 1)]
+        x0 = xc[first].masked_fill(empty, 0)
+        d = xc[src] - x0[dst]
+        m = zeros.index_add(0, dst, d) / degc
+        dev = d - m[dst]
+        var = zeros.index_add(0, dst, dev * dev) / degc
+        mean = x0 + m
+        std = torch.sqrt(var + eps)
+        rstd = (1.0 / std).masked_fill(empty, 0)
+        std = std.masked_fill(empty, 0)
+    mx, amx = seg_max(xc, rowptr, colidx, num_rows, "max")
+    mn, amn = seg_max(xc, rowptr, colidx, num_rows, "min")
+    out = torch.cat([mean, std, mx, mn], 1).to(x.dtype)
+    return out, torch.cat([mean, rstd], 1), torch.cat([amx, amn], 1)
+
+
+def seg_stats_grad(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor,
+                   arg: torch.Tensor, rowptr: torch.Tensor,
+                   colidx: torch.Tensor, num_src: int) -> torch.Tensor:
+    """Gradient of seg_stats wrt x from dy [num_rows, 4*D] and the saved
+    stats and arg: every edge (u, v) carries
+    g_mean[v]/deg_v + g_std[v]*(x[u]-mean[v])*rstd[v]/deg_v, and the max
+    and min blocks route whole to their winning edge (seg_max_grad)."""
+    ct = stats.dtype
+    D = x.shape[1]
+    num_rows = dy.shape[0]
+    g_mean, g_std, g_max, g_min = (t.to(ct) for t in dy.split(D, 1))
+    mean, rstd = stats.split(D, 1)
+    amx, amn = arg.split(D, 1)
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=x.device), deg)
+    src = colidx.to(torch.long)
+    inv = 1.0 / deg.clamp(min=1).to(ct).unsqueeze(1)
+    a = g_std * rstd * inv
+    term = (g_mean * inv)[dst] + a[dst] * (x.to(ct)[src] - mean[dst])
+    dx = torch.zeros(num_src, D, dtype=ct, device=x.device)
+    dx.index_add_(0, src, term)
+    dx += seg_max_grad(g_max, amx, rowptr, colidx, num_src)
+    dx += seg_max_grad(g_min, amn, rowptr, colidx, num_src)
+    return dx.to(dy.dtype)
+
+
 def graph_attention(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
                     colidx: torch.Tensor, num_rows: int, heads: int,
                     scale: float) -> torch.Tensor:

@@ -155,7 +155,7 @@ class _GatherAggregate(torch.autograd.Function):
 
 
 class _GatherBlocks(torch.autograd.Function):
-    """Differentiable exchange for the allgather-mode max/min path:
+    """Differentiable exchange for the allgather-mode max/min/stats path:
     forward all_gathers the padded local blocks into the gather space
     [ws * ag_max_rows, D]; backward reduce_scatters the gather-space
     gradient back to its owners."""
@@ -186,25 +186,36 @@ class _GatherBlocks(torch.autograd.Function):
 
 
 def _aggregate_reduce(x, shard, reduce, group):
-    """max / min neighbor aggregation of the local block. The exchange
-    completes before the local op starts: there is no comm/compute-overlap
-    variant here (merging partial extrema and their args across the
-    self/remote edge split is a follow-up), whatever ROC_OVERLAP /
-    ROC_AG_OVERLAP say."""
+    """max / min / stats neighbor aggregation of the local block. The
+    exchange completes before the local op starts: there is no
+    comm/compute-overlap variant here (merging partial extrema, their args
+    and the shifted sums across the self/remote edge split is a
+    follow-up), whatever ROC_OVERLAP / ROC_AG_OVERLAP say."""
     from ..ops import functional as Fn
+    if reduce == "stats":
+        def local(xe):
+            return Fn.scatter_gather_stats(xe, shard)
+
+        def over_csr(xe, *csr, **order):
+            return Fn.seg_stats_csr(xe, *csr, **order)
+    else:
+        def local(xe):
+            return Fn.scatter_gather_reduce(xe, shard, reduce)
+
+        def over_csr(xe, *csr, **order):
+            return Fn.seg_reduce_csr(xe, *csr, reduce=reduce, **order)
     if shard.world_size == 1:
-        return Fn.scatter_gather_reduce(x, shard, reduce)
+        return local(x)
     if shard.comm_mode == "allgather":
         gathered = _GatherBlocks.apply(x, shard, group)
         cuda = x.is_cuda
-        return Fn.seg_reduce_csr(
+        return over_csr(
             gathered, shard.rowptr, shard.ag_colidx, shard.ag_t_rowptr,
             shard.ag_t_colidx, shard.ag_t_edge_perm32, shard.n_local,
-            shard.world_size * shard.ag_max_rows, reduce,
-            shard.row_order if cuda else None,
-            shard.ag_t_row_order if cuda else None)
-    xe = halo_exchange(x, shard, group)
-    return Fn.scatter_gather_reduce(xe, shard, reduce)
+            shard.world_size * shard.ag_max_rows,
+            row_order=shard.row_order if cuda else None,
+            t_row_order=shard.ag_t_row_order if cuda else None)
+    return local(halo_exchange(x, shard, group))
 
 
 def aggregate(x, shard, dst_scale=None, group=None, reduce="sum"):
@@ -212,9 +223,11 @@ def aggregate(x, shard, dst_scale=None, group=None, reduce="sum"):
     Returns [n_local, D]. reduce="sum" (+ optional fused dst-side degree
     scale) is the sum / mean path; reduce="max" | "min" takes the
     elementwise extremum over in-neighbors (first edge wins ties, empty
-    rows give 0; see ops.functional.scatter_gather_reduce) and takes no
-    dst_scale. max / min exchange first and aggregate after, in every
-    comm mode: they have no comm/compute-overlap variant yet."""
+    rows give 0; see ops.functional.scatter_gather_reduce);
+    reduce="stats" returns [n_local, 4*D], the PNA aggregators
+    [mean | std | max | min] (ops.functional.scatter_gather_stats).
+    Neither takes a dst_scale. They exchange first and aggregate after, in
+    every comm mode: they have no comm/compute-overlap variant yet."""
     from ..ops import functional as Fn
     if reduce != "sum":
         if dst_scale is not None:

@@ -10,7 +10,7 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|transformer, --norm none|layer, --dtype,
+--model gcn|sage|gin|gat|transformer|pna, --norm none|layer, --dtype,
 --checkpoint/--resume, --trace.
 """
 import argparse
@@ -46,7 +46,7 @@ def parse_args():
                          "e.g. 602-256-41")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
-    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "transformer", "sgc",
+    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "transformer", "pna", "sgc",
                              "appnp"])
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
@@ -157,10 +157,10 @@ def parse_args():
     if args.norm not in ("none", "layer"):  # a YAML value
         ap.error(f"--norm must be none or layer, got {args.norm!r}")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
-                                                  "transformer"):
-        ap.error(f"--norm {args.norm} needs --model gcn, sage, gin or "
-                 f"transformer: --model {args.model} has no hidden-layer "
-                 f"norm")
+                                                  "transformer", "pna"):
+        ap.error(f"--norm {args.norm} needs --model gcn, sage, gin, "
+                 f"transformer or pna: --model {args.model} has no "
+                 f"hidden-layer norm")
     return args
 
 
@@ -255,6 +255,13 @@ def main():
         mkw = {"k": args.k_hops}
     elif args.model == "sage":
         mkw = {"aggr": args.aggr}
+    elif args.model == "pna":
+        if g is None:
+            sys.exit("--model pna takes its degree scale delta from the "
+                     "whole graph; it is not available with windowed --file "
+                     "loading (world>1)")
+        from roc_amd import pna_delta
+        mkw = {"delta": pna_delta(g)}
     elif args.model == "appnp":
         mkw = {"alpha": args.alpha}
         if args.k_hops:
