@@ -7,7 +7,8 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           c10::optional<torch::Tensor> row_order, bool accumulate,
           int64_t col_base, int64_t ncols,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
-          c10::optional<torch::Tensor> final_out);
+          c10::optional<torch::Tensor> final_out,
+          c10::optional<torch::Tensor> out_rows);
 void rowscale(torch::Tensor out, torch::Tensor x, torch::Tensor scale);
 void cast_rowscale(torch::Tensor out, torch::Tensor x,
                    c10::optional<torch::Tensor> scale);
@@ -103,7 +104,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("col_base") = 0, pybind11::arg("ncols") = 0,
         pybind11::arg("heavy_rows") = pybind11::none(),
         pybind11::arg("heavy_min") = 0,
-        pybind11::arg("final_out") = pybind11::none());
+        pybind11::arg("final_out") = pybind11::none(),
+        pybind11::arg("out_rows") = pybind11::none());
   m.def("rowscale", &rowscale);
   m.def("cast_rowscale", &cast_rowscale,
         "fp32 -> bf16 cast with optional row scale (strip epilogue)",

@@ -20,6 +20,8 @@
 //  - source-strip passes (fp32 partials) start the rows that are heavy in
 //    their strip first, from a short list, and the last pass stores the
 //    bf16 result itself (HEAVY / FINAL variants of spmm_kernel)
+//  - a degree-ordered strip plan keeps its partials in plan order and
+//    stores finished rows through a row map (PERM variant)
 //
 // The vector path and the (rare) partial-unit tail path are fully
 // separated: the hot path's per-slot buffers are only ever statically
@@ -137,8 +139,15 @@ __device__ void row_accum_tail(
 //  FINAL  last strip pass: the finished row goes to `final_out` as bf16
 //         (after the optional deg_dst scale) and the fp32 partials are
 //         only read — the separate cast pass over memory disappears.
+//  PERM   the rows of this launch are positions of a degree-ordered plan
+//         (partition.build_strip_plan_ordered): row `pos` of the CSR (and
+//         of the fp32 partials a FINAL pass reads) is row out_rows[pos] of
+//         the destination — `final_out` with FINAL, else `out` — and of
+//         deg_dst. Passes 1..K-1 of such a plan are the plain kernel over
+//         a buffer in plan order; only the pass that stores a finished row
+//         pays the index load. An entry outside [0, n_out) is skipped.
 template <typename T, typename OT, int TEAM, int UN, bool BUF, Weight W,
-          bool HEAVY = false, bool FINAL = false>
+          bool HEAVY = false, bool FINAL = false, bool PERM = false>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(
     OT* __restrict__ out, const T* __restrict__ x,
     const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
@@ -146,7 +155,8 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
     const int* __restrict__ row_order, int num_rows, int64_t ld,
     int64_t col_base, int64_t col_end, bool accumulate, unsigned x_bytes,
     const int* __restrict__ heavy_rows, int num_heavy, int heavy_min,
-    unsigned short* __restrict__ final_out) {
+    unsigned short* __restrict__ final_out,
+    const int* __restrict__ out_rows, int n_out) {
   constexpr int EPU = EltTraits<T>::kPerVec;
   const RowTeam<TEAM> rt;
 
@@ -157,9 +167,10 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
       full ? EPU : (col0 < col_end ? (int)(col_end - col0) : 0);
 
   if (full) {
-    auto do_row = [&](int row, int64_t e0, int64_t e1) {
+    // dst: the row of the finished result (== row without PERM)
+    auto do_row = [&](int row, int dst, int64_t e0, int64_t e1) {
       float acc[EPU];
-      OT* o = out + (int64_t)row * ld + col0;
+      OT* o = out + (int64_t)(FINAL ? row : dst) * ld + col0;
       if (accumulate) {  // strip / halo-overlap pass 2: from partials
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] = elt_to_f32(o[j]);
@@ -170,11 +181,11 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
       const auto g = make_gather<T, BUF>(x, x_bytes, ld, col0);
       row_accum_vec<T, UN, W>(acc, g, colidx, weight, e0, e1);
       if (deg_dst) {
-        const float s = deg_dst[row];
+        const float s = deg_dst[dst];
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] *= s;
       }
-      if constexpr (FINAL) store_vec(final_out + (int64_t)row * ld + col0, acc);
+      if constexpr (FINAL) store_vec(final_out + (int64_t)dst * ld + col0, acc);
       else store_vec(o, acc);
     };
     if constexpr (HEAVY) {
@@ -198,27 +209,38 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
         const int64_t e0 = rowptr[row];
         const int64_t e1 = rowptr[row + 1];
         if (!from_list && e1 - e0 >= heavy_min) continue;  // done above
-        do_row(row, e0, e1);
+        do_row(row, row, e0, e1);
+      }
+    } else if constexpr (PERM) {
+      for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
+        const int dst = out_rows[ri];
+        if ((unsigned)dst >= (unsigned)n_out) continue;  // bad entry
+        do_row(ri, dst, rowptr[ri], rowptr[ri + 1]);
       }
     } else {
       for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
         const int row = row_order ? row_order[ri] : ri;
-        do_row(row, rowptr[row], rowptr[row + 1]);
+        do_row(row, row, rowptr[row], rowptr[row + 1]);
       }
     }
   } else if (nvalid > 0) {
     // cold path: natural sweep whatever the schedule variant
     for (int ri = rt.team; ri < num_rows; ri += rt.nteams) {
-      const int row = row_order ? row_order[ri] : ri;
+      const int row = !PERM && row_order ? row_order[ri] : ri;
+      int dst = row;
+      if constexpr (PERM) {
+        dst = out_rows[ri];
+        if ((unsigned)dst >= (unsigned)n_out) continue;  // bad entry
+      }
       float acc[EPU];
-      OT* o = out + (int64_t)row * ld + col0;
+      OT* o = out + (int64_t)(FINAL ? row : dst) * ld + col0;
       for (int j = 0; j < nvalid; ++j)
         acc[j] = accumulate ? elt_to_f32(o[j]) : 0.f;
       row_accum_tail<T, W>(acc, x, ld, col0, nvalid, colidx, weight,
                            rowptr[row], rowptr[row + 1]);
-      const float s = deg_dst ? deg_dst[row] : 1.f;
+      const float s = deg_dst ? deg_dst[dst] : 1.f;
       if constexpr (FINAL) {
-        unsigned short* fo = final_out + (int64_t)row * ld + col0;
+        unsigned short* fo = final_out + (int64_t)dst * ld + col0;
         for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, fo + j);
       } else {
         for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
@@ -270,10 +292,12 @@ struct StripPass {
   int num_heavy = 0;
   int heavy_min = 0;
   unsigned short* final_out = nullptr;
+  const int* out_rows = nullptr;  // plan position -> destination row
+  int n_out = 0;                  // rows of the destination
 };
 
 template <typename T, typename OT, int UN, Weight W, bool HEAVY = false,
-          bool FINAL = false>
+          bool FINAL = false, bool PERM = false>
 void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
                  const int* colidx, const float* deg_dst, const float* weight,
                  const c10::optional<torch::Tensor>& row_order, int num_rows,
@@ -289,10 +313,11 @@ void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
   dispatch_gather(g, [&](auto team_c, auto buf_c) {
     hipLaunchKernelGGL(
         (spmm_kernel<T, OT, decltype(team_c)::value, UN,
-                     decltype(buf_c)::value, W, HEAVY, FINAL>),
+                     decltype(buf_c)::value, W, HEAVY, FINAL, PERM>),
         g.grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
         weight, order, num_rows, ld, col_base, col_end, accumulate, g.bytes,
-        sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out);
+        sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out, sp.out_rows,
+        sp.n_out);
   });
 }
 
@@ -417,7 +442,8 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           c10::optional<torch::Tensor> row_order, bool accumulate,
           int64_t col_base, int64_t ncols,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
-          c10::optional<torch::Tensor> final_out) {
+          c10::optional<torch::Tensor> final_out,
+          c10::optional<torch::Tensor> out_rows) {
   check_mat_pair(out, "out", x, "x", "spmm");
   // strip-pass extras: heavy-first schedule and fused final bf16 store
   StripPass sp;
@@ -445,7 +471,11 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
     ROC_CHECK_DEV_CONT(*final_out);
     TORCH_CHECK(final_out->scalar_type() == torch::kBFloat16,
                 "spmm: final_out must be bf16");
-    TORCH_CHECK(final_out->sizes() == out.sizes(),
+    TORCH_CHECK(out_rows.has_value()
+                    ? final_out->dim() == 2 &&
+                          final_out->size(1) == out.size(1) &&
+                          final_out->size(0) < INT_MAX
+                    : final_out->sizes() == out.sizes(),
                 "spmm: final_out shape mismatch");
     TORCH_CHECK(col_base == 0 && ncols == 0,
                 "spmm: final_out needs a whole-row pass");
@@ -455,9 +485,32 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
                   (out.scalar_type() == torch::kFloat32 &&
                    x.scalar_type() == torch::kBFloat16),
               "spmm: dtype mismatch (out must match x, or be fp32 for bf16 x)");
-  const int num_rows = (int)out.size(0);
+  // with out_rows the CSR (and the partials of a final pass) is in plan
+  // order and may cover fewer rows than the destination
+  const int num_rows =
+      out_rows.has_value() ? (int)out_rows->numel() : (int)out.size(0);
   const int64_t D = out.size(1);
   check_csr(rowptr, colidx, num_rows, "spmm");
+  if (out_rows.has_value()) {
+    ROC_CHECK_DEV_CONT(*out_rows);
+    TORCH_CHECK(out_rows->scalar_type() == torch::kInt32,
+                "spmm: out_rows must be int32");
+    TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && !deg_src.has_value() &&
+                    (final_out.has_value() ||
+                     out.scalar_type() == torch::kBFloat16),
+                "spmm: out_rows is an option of the bf16 plain pass and of "
+                "the final strip pass: bf16 x, no deg_src");
+    TORCH_CHECK(!row_order.has_value() && !heavy_rows.has_value(),
+                "spmm: out_rows excludes row_order and heavy_rows");
+    TORCH_CHECK(col_base == 0 && ncols == 0,
+                "spmm: out_rows needs a whole-row pass");
+    TORCH_CHECK(!final_out.has_value() || out.size(0) == num_rows,
+                "spmm: out_rows must have one entry per row of the partials");
+    sp.out_rows = out_rows->data_ptr<int>();
+    sp.n_out = (int)(final_out.has_value() ? final_out->size(0) : out.size(0));
+    TORCH_CHECK(!deg_dst.has_value() || deg_dst->numel() == sp.n_out,
+                "spmm: deg_dst must have one entry per destination row");
+  }
   // column-phase pass: touch only [col_base, col_base+ncols) of every
   // row (ncols == 0 -> the whole row). The stride stays D.
   const int64_t col_end = ncols > 0 ? col_base + ncols : D;
@@ -475,9 +528,9 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
         auto go = [&](auto un_c, auto w_c) {
           constexpr int UN = decltype(un_c)::value;
           constexpr Weight W = decltype(w_c)::value;
-          auto launch = [&](auto heavy_c, auto final_c) {
+          auto launch = [&](auto heavy_c, auto final_c, auto perm_c) {
             launch_spmm<T, OT, UN, W, decltype(heavy_c)::value,
-                        decltype(final_c)::value>(
+                        decltype(final_c)::value, decltype(perm_c)::value>(
                 (OT*)out.data_ptr(), (const T*)x.data_ptr(),
                 rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
                 opt_ptr<float>(deg_dst), ds, row_order, num_rows, D,
@@ -488,15 +541,29 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           // (checked above), so nothing else is instantiated with them
           if constexpr (std::is_same_v<T, unsigned short> &&
                         std::is_same_v<OT, float> && W == Weight::kNone) {
+            if (sp.out_rows) {  // checked above: a final pass, no list
+              launch(std::false_type{}, std::true_type{}, std::true_type{});
+              return;
+            }
             if (sp.heavy || sp.final_out) {
               dispatch_bool(sp.heavy, [&](auto heavy_c) {
-                dispatch_bool(sp.final_out != nullptr,
-                              [&](auto final_c) { launch(heavy_c, final_c); });
+                dispatch_bool(sp.final_out != nullptr, [&](auto final_c) {
+                  launch(heavy_c, final_c, std::false_type{});
+                });
               });
               return;
             }
           }
-          launch(std::false_type{}, std::false_type{});
+          // the light pass of an ordered plan: plain bf16 -> bf16
+          if constexpr (std::is_same_v<T, unsigned short> &&
+                        std::is_same_v<OT, unsigned short> &&
+                        W == Weight::kNone) {
+            if (sp.out_rows) {
+              launch(std::false_type{}, std::false_type{}, std::true_type{});
+              return;
+            }
+          }
+          launch(std::false_type{}, std::false_type{}, std::false_type{});
         };
         auto by_weight = [&](auto un_c) {
           if (ds) go(un_c, std::integral_constant<Weight, Weight::kSrc>{});

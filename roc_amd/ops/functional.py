@@ -108,7 +108,42 @@ def _hip(x: torch.Tensor) -> bool:
 # ScatterGather (CSR SpMM neighbor aggregation) — the hot op
 # ---------------------------------------------------------------------------
 
-def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0):
+def _order_applies(x) -> bool:
+    """The ordered plan serves whole-row bf16 passes only. The shard holds
+    no natural plan next to it, so every other caller (fp32, D % 8 != 0,
+    column phases) takes the one-pass kernel on the full CSR — the same
+    fp32 adds in the same order."""
+    return (x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0
+            and not _phase_cols())
+
+
+def _strip_spmm_ordered(x, strips, num_rows, row_scale, order):
+    """The strip SpMM on a degree-ordered plan
+    (partition.build_strip_plan_ordered): the light rows in one plain
+    pass, then the heavy region's K-1 accumulate passes over fp32 partials
+    kept in plan order, then its final pass; the light and the final pass
+    store their bf16 rows through the plan's permutation into one out."""
+    perm_heavy, perm_light, lrp, lci = order
+    D = x.shape[1]
+    out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
+    if perm_light.numel():
+        _C.spmm(out, x, lrp, lci, row_scale, None, None, False, 0, 0, None,
+                0, None, perm_light)
+    n_heavy = perm_heavy.numel()
+    if n_heavy:
+        out32 = torch.empty(n_heavy, D, dtype=torch.float32, device=x.device)
+        last = len(strips) - 1
+        for i, (srp, sci) in enumerate(strips):
+            if i < last:
+                _C.spmm(out32, x, srp, sci, None, None, None, i > 0)
+            else:
+                _C.spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
+                        0, 0, None, 0, out, perm_heavy)
+    return out
+
+
+def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
+                order=None):
     """Source-strip-blocked SpMM: each pass gathers from an L2-resident
     source window; partials accumulate in fp32 (one rounding total —
     same numerics as single-pass). Wide feature dims additionally sweep
@@ -119,7 +154,11 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0):
     x.dtype and applies the optional fp32 row_scale; for bf16 the last
     whole-row pass does that itself (final_out) and no cast pass runs.
     heavy: per-strip heavy-first row lists with their threshold
-    (partition.build_strip_heavy), bf16 passes only."""
+    (partition.build_strip_heavy), bf16 passes only.
+    order: the strips are a degree-ordered plan (_strip_spmm_ordered)."""
+    if order is not None:
+        assert _order_applies(x), "ordered strip plan: whole-row bf16 only"
+        return _strip_spmm_ordered(x, strips, num_rows, row_scale, order)
     D = x.shape[1]
     out32 = torch.empty(num_rows, D, dtype=torch.float32, device=x.device)
     ph = _phase_cols()
@@ -163,14 +202,15 @@ class _SpMM(torch.autograd.Function):
     def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, num_rows, num_ext,
                 deg_dst, deg_src, row_order, t_row_order,
                 fwd_strips=None, bwd_strips=None, fwd_heavy=None,
-                bwd_heavy=None, heavy_min=0):
+                bwd_heavy=None, heavy_min=0, fwd_order=None, bwd_order=None):
         ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src, t_row_order)
         ctx.num_ext = num_ext
         ctx.bwd_strips = bwd_strips
-        ctx.bwd_heavy = (bwd_heavy, heavy_min)
-        if _hip(x) and fwd_strips is not None and deg_src is None:
+        ctx.bwd_heavy = (bwd_heavy, heavy_min, bwd_order)
+        if (_hip(x) and fwd_strips is not None and deg_src is None
+                and (fwd_order is None or _order_applies(x))):
             out = _strip_spmm(x, fwd_strips, num_rows, deg_dst, fwd_heavy,
-                              heavy_min)
+                              heavy_min, fwd_order)
         elif _hip(x):
             out = torch.empty(num_rows, x.shape[1], dtype=x.dtype, device=x.device)
             _C.spmm(out, x, rowptr, colidx, deg_dst, deg_src, row_order)
@@ -195,7 +235,8 @@ class _SpMM(torch.autograd.Function):
                 tmp = torch.empty_like(dy)
                 _C.rowscale(tmp, dy, deg_dst)
                 dy = tmp
-            if ctx.bwd_strips is not None and deg_src is None:
+            if (ctx.bwd_strips is not None and deg_src is None
+                    and (ctx.bwd_heavy[2] is None or _order_applies(dy))):
                 dx = _strip_spmm(dy, ctx.bwd_strips, ctx.num_ext, None,
                                  *ctx.bwd_heavy)
             else:
@@ -209,7 +250,7 @@ class _SpMM(torch.autograd.Function):
             dx = ref.spmm(yin, t_rowptr, t_colidx, ctx.num_ext)
             if deg_src is not None:
                 dx = dx * deg_src.unsqueeze(1).to(dx.dtype)
-        return (dx,) + (None,) * 15
+        return (dx,) + (None,) * 17
 
 
 class _SpMMEdge(torch.autograd.Function):
@@ -416,6 +457,8 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
         getattr(shard, "fwd_strip_heavy", None),
         getattr(shard, "bwd_strip_heavy", None),
         getattr(shard, "strip_heavy_min", 0),
+        getattr(shard, "fwd_strip_order", None),
+        getattr(shard, "bwd_strip_order", None),
     )
 
 

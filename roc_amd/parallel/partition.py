@@ -108,6 +108,12 @@ class GraphShard:
     fwd_strip_heavy: Optional[list] = None
     bwd_strip_heavy: Optional[list] = None
     strip_heavy_min: int = 0
+    # degree-ordered plan (build_strip_plan_ordered) of a skewed CSR:
+    # [perm_heavy, perm_light, light_rowptr, light_colidx]. With it the
+    # *_strips of that CSR cover the heavy positions only and it has no
+    # heavy lists. None = natural plan.
+    fwd_strip_order: Optional[list] = None
+    bwd_strip_order: Optional[list] = None
 
     def to(self, device) -> "GraphShard":
         d = {}
@@ -258,6 +264,123 @@ def build_strip_heavy(strips, heavy_min: int):
         rows = rows[np.argsort(-seg[rows], kind="stable")]
         heavy.append(torch.from_numpy(rows.astype(np.int32)))
     return heavy
+
+
+_STRIP_ORDER: Optional[bool] = None
+# Total degree below which a row of an ordered plan is aggregated in one
+# pass instead of one pass per strip. Swept 0..960 at Reddit shape
+# (profiles/r44): 128 is the best cell at D=256 (64 is 2% behind, 240
+# within 0.2%) and ties with 64 for the best ordered cell at D=64; from
+# 480 up the light pass's L2 misses cost more than the partials saved.
+LIGHT_DEG_DEFAULT = 128
+_LIGHT_DEG: Optional[int] = None
+# The ordered plan was measured at the Reddit shape only, so it has the
+# default strip guard as a guard of its own: lowering
+# ROC_SPMM_STRIP_MIN_EDGES alone (debugging, toy graphs) keeps the natural
+# plan.
+STRIP_ORDER_MIN_EDGES = 24_000_000
+
+
+def strip_order_on() -> bool:
+    """Build degree-ordered strip plans for skewed CSRs
+    (ROC_SPMM_STRIP_ORDER, 1/0). Pinned at first use."""
+    global _STRIP_ORDER
+    if _STRIP_ORDER is None:
+        _STRIP_ORDER = os.environ.get("ROC_SPMM_STRIP_ORDER", "1") != "0"
+    return _STRIP_ORDER
+
+
+def strip_light_deg() -> int:
+    """Total in-degree below which a row of an ordered plan is light: one
+    plain pass over its whole edge list, no fp32 partials
+    (ROC_SPMM_LIGHT_DEG, 0 = no light pass). Pinned at first use."""
+    global _LIGHT_DEG
+    if _LIGHT_DEG is None:
+        _LIGHT_DEG = max(0, int(os.environ.get("ROC_SPMM_LIGHT_DEG",
+                                               str(LIGHT_DEG_DEFAULT))))
+    return _LIGHT_DEG
+
+
+def rows_sorted(rowptr: torch.Tensor, colidx: torch.Tensor) -> bool:
+    """True when the columns of every row are non-decreasing — what the
+    strip plans rely on to cut a row into contiguous segments."""
+    rp = rowptr.numpy()
+    ci = colidx.numpy()
+    if ci.shape[0] < 2:
+        return True
+    down = np.nonzero(ci[1:] < ci[:-1])[0] + 1  # a drop may only start a row
+    starts = np.zeros(ci.shape[0] + 1, dtype=bool)
+    starts[rp] = True
+    return bool(starts[down].all())
+
+
+def build_strip_plan_ordered(rowptr: torch.Tensor, colidx: torch.Tensor,
+                             num_cols: int, width: int, light_deg: int):
+    """Strip plan over the rows sorted by total degree, descending (stable).
+
+    Returns (perm, n_heavy, strips, light):
+      perm     int32 [N]: position i of the plan is row perm[i]
+      n_heavy  rows with degree >= light_deg (light_deg 0: every row)
+      strips   [(srp, sci)] per source strip over positions [0, n_heavy):
+               segment i of strip s is row perm[i]'s edges with source in
+               [s*width, (s+1)*width), in their original order
+      light    one CSR (rp, ci) over positions [n_heavy, N), each row's
+               whole edge list in its original order
+
+    The fp32 partials of the strip passes are private to the SpMM, so they
+    live in plan order: a pass's natural sweep then starts the longest rows
+    first and gives every wave rows of about equal length, with no index
+    load and a streaming partial read-modify-write. Only the last pass and
+    the light pass store through perm. A row's strip segments in strip
+    order are its edge list in ascending order, so strips or one pass is
+    the same sequence of fp32 adds: light rows skip the partials traffic
+    and the per-strip frame for a handful of edges each."""
+    assert rows_sorted(rowptr, colidx), \
+        "strip plans need non-decreasing columns in every row"
+    rp = rowptr.numpy()
+    ci = colidx.numpy()
+    deg = np.diff(rp)
+    n = deg.shape[0]
+    perm = np.argsort(-deg, kind="stable")
+    n_heavy = n if light_deg <= 0 else int((deg >= light_deg).sum())
+    pdeg = deg[perm]
+    prp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(pdeg, out=prp[1:])
+    if prp[-1]:
+        idx = np.repeat(rp[:-1][perm] - prp[:-1], pdeg) + np.arange(
+            int(prp[-1]), dtype=np.int64)
+        pci = ci[idx]
+    else:
+        pci = np.empty(0, dtype=ci.dtype)
+    cut = int(prp[n_heavy])
+    strips = build_strip_plan(
+        torch.from_numpy(prp[:n_heavy + 1].copy()),
+        torch.from_numpy(np.ascontiguousarray(pci[:cut])), num_cols, width)
+    light = (torch.from_numpy(prp[n_heavy:] - cut),
+             torch.from_numpy(np.ascontiguousarray(pci[cut:])))
+    return torch.from_numpy(perm.astype(np.int32)), n_heavy, strips, light
+
+
+def strip_rows_skewed(rowptr: torch.Tensor, colidx: torch.Tensor,
+                      width: int, heavy_min: int, light_deg: int) -> bool:
+    """Whether a CSR's rows are skewed enough for the ordered plan: its
+    natural plan would list heavy rows in some strip (a segment of
+    >= heavy_min edges), or it has light rows. Poisson-like rows (the
+    Reddit-shape transpose) are neither and keep the natural plan."""
+    rp = rowptr.numpy()
+    deg = np.diff(rp)
+    if deg.shape[0] == 0:
+        return False
+    if light_deg > 0 and int(deg.min()) < light_deg:
+        return True
+    if heavy_min <= 0 or int(deg.max()) < heavy_min:
+        return False
+    # longest strip segment of any row
+    ci = colidx.numpy()
+    k = int(ci.max()) // width + 1
+    key = np.repeat(np.arange(deg.shape[0], dtype=np.int64) * k, deg)
+    key += ci // width
+    return int(np.bincount(key).max()) >= heavy_min
 
 
 def edge_tensor(shard: GraphShard, dim: Optional[int] = None,
@@ -612,17 +735,33 @@ def build_shard_from_window(rowptr_full: torch.Tensor,
     n_strips = (n_ext + strip_w - 1) // max(strip_w, 1)
     if (strip_w > 0 and colidx_t.numel() >= strip_min
             and 2 <= n_strips <= max_k):
-        shard_kw["fwd_strips"] = build_strip_plan(rowptr_t, colidx_t,
-                                                  n_ext, strip_w)
-        shard_kw["bwd_strips"] = build_strip_plan(t_rowptr, t_colidx,
-                                                  n_local, strip_w)
         heavy_min = strip_heavy_min()
         if heavy_min > 0:
-            shard_kw["fwd_strip_heavy"] = build_strip_heavy(
-                shard_kw["fwd_strips"], heavy_min)
-            shard_kw["bwd_strip_heavy"] = build_strip_heavy(
-                shard_kw["bwd_strips"], heavy_min)
             shard_kw["strip_heavy_min"] = heavy_min
+        # Per CSR, one plan on the device: the degree-ordered one where the
+        # rows are skewed, else the natural one with its heavy lists. A
+        # "natural" row schedule was picked for gather locality, which a
+        # degree sort would undo; column phases sweep the natural plan.
+        want_order = (strip_order_on() and sched != "natural"
+                      and not phase_on
+                      and colidx_t.numel() >= STRIP_ORDER_MIN_EDGES)
+        for pfx, rp_, ci_, ncols in (("fwd", rowptr_t, colidx_t, n_ext),
+                                     ("bwd", t_rowptr, t_colidx, n_local)):
+            if want_order and strip_rows_skewed(rp_, ci_, strip_w, heavy_min,
+                                                strip_light_deg()):
+                if not rows_sorted(rp_, ci_):
+                    continue  # no strips at all on unsorted rows
+                perm, n_heavy, strips, light = build_strip_plan_ordered(
+                    rp_, ci_, ncols, strip_w, strip_light_deg())
+                shard_kw[pfx + "_strips"] = strips
+                shard_kw[pfx + "_strip_order"] = [
+                    perm[:n_heavy], perm[n_heavy:], light[0], light[1]]
+                continue
+            shard_kw[pfx + "_strips"] = build_strip_plan(rp_, ci_, ncols,
+                                                         strip_w)
+            if heavy_min > 0:
+                shard_kw[pfx + "_strip_heavy"] = build_strip_heavy(
+                    shard_kw[pfx + "_strips"], heavy_min)
 
     return GraphShard(
         rank=rank, world_size=world_size, bounds=list(bounds),
