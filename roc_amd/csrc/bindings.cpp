@@ -79,6 +79,24 @@ void graph_attn_bwd_src(torch::Tensor dkv, torch::Tensor q, torch::Tensor dy,
                         torch::Tensor t_colidx,
                         c10::optional<torch::Tensor> t_row_order,
                         int64_t heads, double scale);
+void gatv2_attn_fwd(torch::Tensor out, c10::optional<torch::Tensor> lse,
+                    torch::Tensor xl, torch::Tensor xr, torch::Tensor att,
+                    torch::Tensor rowptr, torch::Tensor colidx,
+                    c10::optional<torch::Tensor> row_order, int64_t heads,
+                    double slope);
+void gatv2_attn_bwd_dst(torch::Tensor dxr, torch::Tensor datt,
+                        torch::Tensor delta, torch::Tensor dy,
+                        torch::Tensor out, torch::Tensor lse, torch::Tensor xl,
+                        torch::Tensor xr, torch::Tensor att,
+                        torch::Tensor rowptr, torch::Tensor colidx,
+                        c10::optional<torch::Tensor> row_order, int64_t heads,
+                        double slope);
+void gatv2_attn_bwd_src(torch::Tensor dxl, torch::Tensor xl, torch::Tensor xr,
+                        torch::Tensor att, torch::Tensor dy, torch::Tensor lse,
+                        torch::Tensor delta, torch::Tensor t_rowptr,
+                        torch::Tensor t_colidx,
+                        c10::optional<torch::Tensor> t_row_order,
+                        int64_t heads, double slope);
 void edge_softmax_fwd(torch::Tensor alpha, torch::Tensor s,
                       torch::Tensor rowptr);
 void edge_softmax_bwd(torch::Tensor ds, torch::Tensor dalpha,
@@ -206,6 +224,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
         pybind11::arg("t_row_order"), pybind11::arg("heads"),
         pybind11::arg("scale"));
+  m.def("gatv2_attn_fwd", &gatv2_attn_fwd,
+        "GATv2 attention over in-neighbours (one gather per edge, online "
+        "softmax); lse = None skips the log-sum-exp store",
+        pybind11::arg("out"), pybind11::arg("lse"), pybind11::arg("xl"),
+        pybind11::arg("xr"), pybind11::arg("att"), pybind11::arg("rowptr"),
+        pybind11::arg("colidx"), pybind11::arg("row_order"),
+        pybind11::arg("heads"), pybind11::arg("slope"));
+  m.def("gatv2_attn_bwd_dst", &gatv2_attn_bwd_dst,
+        "GATv2 gradient, destination-major pass: delta, dxr, and datt by an "
+        "order-fixed slab fold",
+        pybind11::arg("dxr"), pybind11::arg("datt"), pybind11::arg("delta"),
+        pybind11::arg("dy"), pybind11::arg("out"), pybind11::arg("lse"),
+        pybind11::arg("xl"), pybind11::arg("xr"), pybind11::arg("att"),
+        pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order"), pybind11::arg("heads"),
+        pybind11::arg("slope"));
+  m.def("gatv2_attn_bwd_src", &gatv2_attn_bwd_src,
+        "GATv2 gradient, source-major pass over the transpose CSR: dxl",
+        pybind11::arg("dxl"), pybind11::arg("xl"), pybind11::arg("xr"),
+        pybind11::arg("att"), pybind11::arg("dy"), pybind11::arg("lse"),
+        pybind11::arg("delta"), pybind11::arg("t_rowptr"),
+        pybind11::arg("t_colidx"), pybind11::arg("t_row_order"),
+        pybind11::arg("heads"), pybind11::arg("slope"));
   m.def("edge_softmax_fwd", &edge_softmax_fwd,
         "per-row segment softmax over edge scores (GAT attention)");
   m.def("edge_softmax_bwd", &edge_softmax_bwd);

@@ -3,6 +3,7 @@ from .sage import GraphSAGE
 from .gin import GIN
 from .gat import GAT
 from .transformer import GraphTransformer
+from .gatv2 import GATv2
 from .sgc import SGC
 from .appnp import APPNP
 from .pna import PNA, pna_delta
@@ -18,6 +19,8 @@ def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
         return GIN(dims, dropout=dropout, seed=seed, **kw)
     if name == "gat":
         return GAT(dims, dropout=dropout, seed=seed, **kw)
+    if name == "gatv2":
+        return GATv2(dims, dropout=dropout, seed=seed, **kw)
     if name == "transformer":
         return GraphTransformer(dims, dropout=dropout, seed=seed, **kw)
     if name == "sgc":

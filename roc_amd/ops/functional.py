@@ -748,6 +748,119 @@ def graph_attention(q, kv, shard, heads: int, scale: Optional[float] = None):
 
 
 # ---------------------------------------------------------------------------
+# GATv2 dynamic attention (fused one-gather kernels)
+# ---------------------------------------------------------------------------
+
+class _GATv2Attention(torch.autograd.Function):
+    """GPU path of gatv2_attention (gatv2_attn.hip). The forward saves out
+    and a fp32 [n, H] log-sum-exp; the backward is two gather passes that
+    recompute z, s and p = exp(s - lse): destination-major for delta, dxr
+    and datt (an order-fixed slab fold, no atomics), source-major over the
+    transpose CSR for dxl, skipped when xl needs no gradient. need_lse is
+    False when nothing needs a gradient (decided by the caller: grad mode
+    is always off in here); the kernel variant without the lse store runs
+    then."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, rowptr, colidx, t_rowptr, t_colidx, heads,
+                slope, row_order, t_row_order, need_lse):
+        out = torch.empty_like(xr)
+        lse = None
+        if need_lse:
+            lse = torch.empty(xr.shape[0], heads, dtype=torch.float32,
+                              device=xr.device)
+        _C.gatv2_attn_fwd(out, lse, xl, xr, att, rowptr, colidx, row_order,
+                          heads, slope)
+        if need_lse:
+            ctx.save_for_backward(xl, xr, att, out, lse, rowptr, colidx,
+                                  t_rowptr, t_colidx, row_order, t_row_order)
+        ctx.heads, ctx.slope = heads, slope
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xl, xr, att, out, lse, rowptr, colidx, t_rowptr, t_colidx, row_order,
+         t_row_order) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dxr = torch.empty_like(xr)
+        datt = torch.empty_like(att)
+        delta = torch.empty_like(lse)
+        _C.gatv2_attn_bwd_dst(dxr, datt, delta, dy, out, lse, xl, xr, att,
+                              rowptr, colidx, row_order, ctx.heads, ctx.slope)
+        dxl = None
+        if ctx.needs_input_grad[0]:
+            dxl = torch.empty_like(xl)
+            _C.gatv2_attn_bwd_src(dxl, xl, xr, att, dy, lse, delta, t_rowptr,
+                                  t_colidx, t_row_order, ctx.heads, ctx.slope)
+        return (dxl, dxr, datt) + (None,) * 9
+
+
+def gatv2_attention_csr(xl, xr, att, rowptr, colidx, t_rowptr, t_colidx,
+                        num_rows, num_src, heads, slope: float = 0.2,
+                        row_order=None, t_row_order=None):
+    """gatv2_attention over an explicit CSR / transpose-CSR pair. Every
+    argument is checked here, before any launch."""
+    heads = int(heads)
+    if xr.dim() != 2 or xr.shape[0] != num_rows:
+        raise ValueError(f"xr must be [{num_rows}, D], got {tuple(xr.shape)}")
+    D = xr.shape[1]
+    if heads < 1 or D < heads or D % heads != 0:
+        raise ValueError(
+            f"feature dim {D} is not a positive multiple of {heads} heads")
+    if tuple(xl.shape) != (num_src, D):
+        # colidx indexes xl unchecked on the GPU: a short xl reads out of
+        # bounds
+        raise ValueError(
+            f"xl must be [{num_src}, {D}], got {tuple(xl.shape)}")
+    if xl.dtype != xr.dtype:
+        raise ValueError(
+            f"xl and xr must share a dtype, got {xl.dtype} and {xr.dtype}")
+    if xr.is_cuda and xr.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(
+            f"gatv2_attention on GPU takes bf16 or fp32, got {xr.dtype}")
+    ok = (torch.float32, torch.float64) if xr.dtype == torch.float64 \
+        else (torch.float32,)
+    if att.dtype not in ok or tuple(att.shape) != (heads, D // heads):
+        raise ValueError(
+            f"att must be fp32 [{heads}, {D // heads}], got {att.dtype} "
+            f"{tuple(att.shape)}")
+    if att.device != xr.device or xl.device != xr.device:
+        raise ValueError("xl, xr and att must live on one device")
+    slope = float(slope)
+    if not _hip(xr):
+        return ref.gatv2_attention(xl, xr, att, rowptr, colidx, num_rows,
+                                   heads, slope)
+    need_lse = torch.is_grad_enabled() and (
+        xl.requires_grad or xr.requires_grad or att.requires_grad)
+    return _GATv2Attention.apply(
+        xl.contiguous(), xr.contiguous(), att.contiguous(), rowptr, colidx,
+        t_rowptr, t_colidx, heads, slope, row_order, t_row_order, need_lse)
+
+
+def gatv2_attention(xl, xr, att, shard, heads: int, slope: float = 0.2):
+    """GATv2 dynamic attention over each node's in-neighbourhood (Brody et
+    al. 2022, PyG's GATv2Conv).
+
+    xl: [n_ext, D], halo-extended, D = heads * dh: the source projection,
+    which is both the score row and the value row. xr: [n_local, D], the
+    destination projection. att: fp32 [heads, dh], used as it is (fp64 is
+    accepted next to fp64 inputs on CPU, for gradcheck). For row v, head h
+    and in-edge e from u_e:
+      s_e = sum_j att[h,j] * lrelu(xl[u_e,h,j] + xr[v,h,j]),
+      alpha = softmax_e(s),  out[v,h,:] = sum_e alpha_e * xl[u_e,h,:]
+    Returns [n_local, D] in xr's dtype (bf16 or fp32 on GPU; all arithmetic
+    is fp32, one rounding at the store). Duplicate edges each count; a row
+    without edges gives 0 and passes no gradient; a source without
+    out-edges gets a zero gradient. The gradient of att is reduced without
+    atomics in a fixed order: bit-reproducible from run to run.
+    `shard` may be a GraphShard or anything with the same CSR fields."""
+    return gatv2_attention_csr(
+        xl, xr, att, shard.rowptr, shard.colidx, shard.t_rowptr,
+        shard.t_colidx, shard.n_local, shard.n_ext, heads, slope,
+        shard.row_order, shard.t_row_order)
+
+
+# ---------------------------------------------------------------------------
 # InDegreeNorm
 # ---------------------------------------------------------------------------
 

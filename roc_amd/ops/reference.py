@@ -215,6 +215,42 @@ def graph_attention(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
     return out.reshape(num_rows, D).to(q.dtype)
 
 
+def gatv2_attention(xl: torch.Tensor, xr: torch.Tensor, att: torch.Tensor,
+                    rowptr: torch.Tensor, colidx: torch.Tensor, num_rows: int,
+                    heads: int, slope: float = 0.2) -> torch.Tensor:
+    """GATv2 dynamic attention over the in-neighbourhood (Brody et al. 2022,
+    PyG's GATv2Conv without its extras; the reference has no attention):
+      s_e = sum_j att[h,j] * lrelu(xl[u_e,h,j] + xr[v,h,j])  for the edges e
+                                                              of row v
+      out[v,h,:] = sum_e softmax_e(s) * xl[u_e,h,:]
+    xl: [n_src, D], D = heads * dh; xr: [num_rows, D]; att: [heads, dh].
+    Duplicate edges each count; a row without edges gives 0. Max-subtracted
+    softmax out of index ops, in fp32 (fp64 stays fp64), differentiable by
+    autograd; the result is cast back to xr's dtype."""
+    ct = torch.float64 if xr.dtype == torch.float64 else torch.float32
+    D = xr.shape[1]
+    dh = D // heads
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=xr.device), deg)
+    src = colidx.to(torch.long)
+    E = int(src.numel())
+    xlh = xl.to(ct).view(xl.shape[0], heads, dh)
+    xrh = xr.to(ct).view(num_rows, heads, dh)
+    z = torch.nn.functional.leaky_relu(xlh[src] + xrh[dst], slope)
+    s = (z * att.to(ct).unsqueeze(0)).sum(dim=2)                 # [E, H]
+    m = torch.zeros(num_rows, heads, dtype=ct, device=xr.device)
+    m = m.scatter_reduce(0, dst.unsqueeze(1).expand(E, heads), s.detach(),
+                         reduce="amax", include_self=False)
+    ex = (s - m[dst]).exp()
+    den = torch.zeros(num_rows, heads, dtype=ct,
+                      device=xr.device).index_add(0, dst, ex)
+    alpha = ex / den[dst]
+    out = torch.zeros(num_rows, heads, dh, dtype=ct, device=xr.device)
+    out = out.index_add(0, dst, alpha.unsqueeze(2) * xlh[src])
+    return out.reshape(num_rows, D).to(xr.dtype)
+
+
 def _ln_compute_dtype(x: torch.Tensor) -> torch.dtype:
     return torch.float64 if x.dtype == torch.float64 else torch.float32
 

@@ -10,7 +10,7 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|transformer|pna, --norm none|layer, --dtype,
+--model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer, --dtype,
 --checkpoint/--resume, --trace.
 """
 import argparse
@@ -46,14 +46,14 @@ def parse_args():
                          "e.g. 602-256-41")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
-    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "transformer", "pna", "sgc",
+    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "gatv2", "transformer", "pna", "sgc",
                              "appnp"])
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
     ap.add_argument("--norm", default="none", choices=["none", "layer"],
                     help="hidden-layer normalization of --model gcn, sage, "
-                         "gin or transformer: layer = fused per-node "
+                         "gin, transformer or gatv2: layer = fused per-node "
                          "LayerNorm + ReLU")
     ap.add_argument("--epochs", "-e", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
@@ -68,7 +68,7 @@ def parse_args():
     ap.add_argument("--eval-every", type=int, default=5)
     ap.add_argument("--residual", action="store_true")
     ap.add_argument("--heads", type=int, default=4,
-                    help="attention heads of --model gat or transformer "
+                    help="attention heads of --model gat, gatv2 or transformer "
                          "(concat; last layer 1)")
     ap.add_argument("--k-hops", type=int, default=None,
                     help="SGC propagation depth (default 2) / APPNP "
@@ -157,9 +157,10 @@ def parse_args():
     if args.norm not in ("none", "layer"):  # a YAML value
         ap.error(f"--norm must be none or layer, got {args.norm!r}")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
-                                                  "transformer", "pna"):
+                                                  "transformer", "gatv2",
+                                                  "pna"):
         ap.error(f"--norm {args.norm} needs --model gcn, sage, gin, "
-                 f"transformer or pna: --model {args.model} has no "
+                 f"transformer, gatv2 or pna: --model {args.model} has no "
                  f"hidden-layer norm")
     return args
 
@@ -249,7 +250,7 @@ def main():
         shard = build_shard(g, rank, world, bounds,
                             use_comm=(world > 1 and dist.is_initialized()))
     mkw = {"residual": args.residual} if args.model == "gcn" else {}
-    if args.model in ("gat", "transformer"):
+    if args.model in ("gat", "gatv2", "transformer"):
         mkw = {"heads": args.heads}
     elif args.model == "sgc" and args.k_hops:
         mkw = {"k": args.k_hops}
