@@ -9,6 +9,15 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
           c10::optional<torch::Tensor> final_out,
           c10::optional<torch::Tensor> out_rows);
+void quantize_rows_fp8(torch::Tensor q, torch::Tensor s, torch::Tensor x,
+                       c10::optional<torch::Tensor> pre_scale);
+void spmm_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor scale,
+              torch::Tensor rowptr, torch::Tensor colidx,
+              c10::optional<torch::Tensor> deg_dst,
+              c10::optional<torch::Tensor> row_order, bool accumulate,
+              c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
+              c10::optional<torch::Tensor> final_out,
+              c10::optional<torch::Tensor> out_rows);
 void rowscale(torch::Tensor out, torch::Tensor x, torch::Tensor scale);
 void cast_rowscale(torch::Tensor out, torch::Tensor x,
                    c10::optional<torch::Tensor> scale);
@@ -120,6 +129,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("row_order") = pybind11::none(),
         pybind11::arg("accumulate") = false,
         pybind11::arg("col_base") = 0, pybind11::arg("ncols") = 0,
+        pybind11::arg("heavy_rows") = pybind11::none(),
+        pybind11::arg("heavy_min") = 0,
+        pybind11::arg("final_out") = pybind11::none(),
+        pybind11::arg("out_rows") = pybind11::none());
+  m.def("quantize_rows_fp8", &quantize_rows_fp8,
+        "bf16 rows (times an optional fp32 row factor) -> e4m3 bytes and a "
+        "power-of-two fp32 scale per row",
+        pybind11::arg("q"), pybind11::arg("s"), pybind11::arg("x"),
+        pybind11::arg("pre_scale") = pybind11::none());
+  m.def("spmm_fp8", &spmm_fp8,
+        "CSR SpMM over e4m3 rows with per-row scales; the options are spmm's",
+        pybind11::arg("out"), pybind11::arg("q"), pybind11::arg("scale"),
+        pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("deg_dst") = pybind11::none(),
+        pybind11::arg("row_order") = pybind11::none(),
+        pybind11::arg("accumulate") = false,
         pybind11::arg("heavy_rows") = pybind11::none(),
         pybind11::arg("heavy_min") = 0,
         pybind11::arg("final_out") = pybind11::none(),

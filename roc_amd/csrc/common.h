@@ -55,6 +55,10 @@ template <>
 struct EltTraits<unsigned short> {  // bf16 storage as raw u16
   static constexpr int kPerVec = 8;  // 8 x bf16 = 16 B
 };
+template <>
+struct EltTraits<unsigned char> {  // OCP fp8 e4m3 storage as raw bytes
+  static constexpr int kPerVec = 16;  // 16 x fp8 = 16 B
+};
 
 // Load EPU elements from a 16B-aligned-or-not location as fp32.
 __device__ __forceinline__ void load_f32x4(const float* p, float* acc_dst) {
@@ -92,6 +96,16 @@ __device__ __forceinline__ void store_vec(float* p, const float (&a)[4]) {
 __device__ __forceinline__ void store_vec(float* p, const float (&a)[8]) {
   store_f32x4(p, a);
   store_f32x4(p + 4, a + 4);
+}
+
+__device__ __forceinline__ void store_vec(unsigned short* p,
+                                          const float (&a)[16]) {
+  store_bf16x8(p, a);
+  store_bf16x8(p + 8, a + 8);
+}
+__device__ __forceinline__ void store_vec(float* p, const float (&a)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; j += 4) store_f32x4(p + j, a + j);
 }
 
 __device__ __forceinline__ float elt_to_f32(float x) { return x; }

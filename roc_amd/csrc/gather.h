@@ -15,12 +15,17 @@ template <typename T>
 struct RawVec { using type = float4; };
 template <>
 struct RawVec<unsigned short> { using type = uint4; };
+template <>
+struct RawVec<unsigned char> { using type = uint4; };  // 16 x fp8 e4m3
 
 __device__ __forceinline__ uint4 load_raw(const unsigned short* p) {
   return *reinterpret_cast<const uint4*>(p);
 }
 __device__ __forceinline__ float4 load_raw(const float* p) {
   return *reinterpret_cast<const float4*>(p);
+}
+__device__ __forceinline__ uint4 load_raw(const unsigned char* p) {
+  return *reinterpret_cast<const uint4*>(p);
 }
 
 // the exact widen of one payload to EPU floats (bf16x8 / f32x4)
@@ -32,6 +37,22 @@ __device__ __forceinline__ void unpack(float* v, const uint4& r) {
 }
 __device__ __forceinline__ void unpack(float* v, const float4& r) {
   v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+}
+
+// fp8 e4m3 (OCP) x16: the hardware widen, two packed converts per payload
+// dword (v_cvt_pk_f32_fp8 on the low and the high byte pair). A bf16 and an
+// fp8 payload are both a uint4, so this one carries its format in its name.
+typedef __attribute__((ext_vector_type(2))) float f32x2v;
+__device__ __forceinline__ void unpack_fp8_dword(float* v, unsigned w) {
+  const f32x2v lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  const f32x2v hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+}
+__device__ __forceinline__ void unpack_fp8(float* v, const uint4& r) {
+  unpack_fp8_dword(v, r.x);
+  unpack_fp8_dword(v + 4, r.y);
+  unpack_fp8_dword(v + 8, r.z);
+  unpack_fp8_dword(v + 12, r.w);
 }
 
 // one unit of winner edge indices (seg_max.hip, seg_stats.hip)

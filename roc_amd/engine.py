@@ -26,11 +26,23 @@ class Trainer:
                  optimizer: AdamOptimizer, device="cpu",
                  compute_dtype: torch.dtype = torch.float32,
                  grad_scale: float = 1.0, group=None, seed: int = 1,
-                 num_classes=None, local_slices: bool = False):
+                 num_classes=None, local_slices: bool = False,
+                 gather_dtype=None):
         # local_slices=True: feats/labels/mask are ALREADY this rank's
         # [lo, hi) rows (windowed dataset loading)
+        # gather_dtype="fp8": the sum aggregations gather e4m3 rows
+        # (ops.functional.scatter_gather). The halo and allgather exchanges
+        # stay bf16, so it is a single-process mode.
+        if gather_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"gather_dtype must be 'bf16' or 'fp8', got "
+                             f"{gather_dtype!r}")
+        if gather_dtype == "fp8" and shard.world_size > 1:
+            raise ValueError("gather_dtype='fp8' needs world size 1: the "
+                             "halo and allgather paths gather bf16 rows")
+        self.gather_dtype = gather_dtype
         self.model = model.to(device)
         self.shard = shard.to(device)
+        self.shard.gather_dtype = gather_dtype
         self.device = torch.device(device)
         self.dtype = compute_dtype
         self.group = group
@@ -311,6 +323,7 @@ class Trainer:
     def load_shard(self, shard, feats, labels, mask, local_slices=False):
         device, dt = self.device, self.dtype
         self.shard = shard.to(device)
+        self.shard.gather_dtype = self.gather_dtype
         lo, hi = (0, shard.n_local) if local_slices else (shard.lo, shard.hi)
         self.x = feats[lo:hi].to(device=device, dtype=dt).contiguous()
         self.labels = labels[lo:hi].to(device=device).contiguous()

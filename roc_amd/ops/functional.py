@@ -117,7 +117,23 @@ def _order_applies(x) -> bool:
             and not _phase_cols())
 
 
-def _strip_spmm_ordered(x, strips, num_rows, row_scale, order):
+def _spmm_launcher(fp8_scale):
+    """_C.spmm, or for e4m3 rows _C.spmm_fp8 bound to their scales behind
+    _C.spmm's positional signature, so one strip driver serves both."""
+    if fp8_scale is None:
+        return _C.spmm
+
+    def run(out, q, rowptr, colidx, deg_dst=None, deg_src=None,
+            row_order=None, accumulate=False, col_base=0, ncols=0,
+            heavy_rows=None, heavy_min=0, final_out=None, out_rows=None):
+        assert deg_src is None and col_base == 0 and ncols == 0
+        _C.spmm_fp8(out, q, fp8_scale, rowptr, colidx, deg_dst, row_order,
+                    accumulate, heavy_rows, heavy_min, final_out, out_rows)
+    return run
+
+
+def _strip_spmm_ordered(x, strips, num_rows, row_scale, order,
+                        fp8_scale=None):
     """The strip SpMM on a degree-ordered plan
     (partition.build_strip_plan_ordered): the light rows in one plain
     pass, then the heavy region's K-1 accumulate passes over fp32 partials
@@ -125,25 +141,26 @@ def _strip_spmm_ordered(x, strips, num_rows, row_scale, order):
     store their bf16 rows through the plan's permutation into one out."""
     perm_heavy, perm_light, lrp, lci = order
     D = x.shape[1]
+    spmm = _spmm_launcher(fp8_scale)
     out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
     if perm_light.numel():
-        _C.spmm(out, x, lrp, lci, row_scale, None, None, False, 0, 0, None,
-                0, None, perm_light)
+        spmm(out, x, lrp, lci, row_scale, None, None, False, 0, 0, None,
+             0, None, perm_light)
     n_heavy = perm_heavy.numel()
     if n_heavy:
         out32 = torch.empty(n_heavy, D, dtype=torch.float32, device=x.device)
         last = len(strips) - 1
         for i, (srp, sci) in enumerate(strips):
             if i < last:
-                _C.spmm(out32, x, srp, sci, None, None, None, i > 0)
+                spmm(out32, x, srp, sci, None, None, None, i > 0)
             else:
-                _C.spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
-                        0, 0, None, 0, out, perm_heavy)
+                spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
+                     0, 0, None, 0, out, perm_heavy)
     return out
 
 
 def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
-                order=None):
+                order=None, fp8_scale=None):
     """Source-strip-blocked SpMM: each pass gathers from an L2-resident
     source window; partials accumulate in fp32 (one rounding total —
     same numerics as single-pass). Wide feature dims additionally sweep
@@ -155,10 +172,18 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
     whole-row pass does that itself (final_out) and no cast pass runs.
     heavy: per-strip heavy-first row lists with their threshold
     (partition.build_strip_heavy), bf16 passes only.
-    order: the strips are a degree-ordered plan (_strip_spmm_ordered)."""
+    order: the strips are a degree-ordered plan (_strip_spmm_ordered).
+    fp8_scale: x is the e4m3 bytes of quantize_rows_fp8 and this its scale
+    vector; the passes are the bf16 whole-row ones on the fp8 kernel (no
+    column phases: the caller takes the one-pass kernel when they are on)."""
+    fp8 = fp8_scale is not None
+    assert not (fp8 and _phase_cols()), "fp8 strip passes: whole rows only"
     if order is not None:
-        assert _order_applies(x), "ordered strip plan: whole-row bf16 only"
-        return _strip_spmm_ordered(x, strips, num_rows, row_scale, order)
+        assert fp8 or _order_applies(x), \
+            "ordered strip plan: whole-row bf16 only"
+        return _strip_spmm_ordered(x, strips, num_rows, row_scale, order,
+                                   fp8_scale)
+    spmm = _spmm_launcher(fp8_scale)
     D = x.shape[1]
     out32 = torch.empty(num_rows, D, dtype=torch.float32, device=x.device)
     ph = _phase_cols()
@@ -166,7 +191,7 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
         phases = [(p, ph) for p in range(0, D, ph)]
     else:
         phases = [(0, 0)]  # one whole-row phase
-    bf16 = x.dtype == torch.bfloat16
+    bf16 = x.dtype == torch.bfloat16 or fp8  # the result is bf16
     fuse_final = bf16 and D % 8 == 0 and phases == [(0, 0)]
     if not bf16:
         heavy = None
@@ -177,11 +202,11 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
             if fuse_final and i == len(strips) - 1:
                 out = torch.empty(num_rows, D, dtype=torch.bfloat16,
                                   device=x.device)
-                _C.spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
-                        0, 0, hv, heavy_min, out)
+                spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
+                     0, 0, hv, heavy_min, out)
             else:
-                _C.spmm(out32, x, srp, sci, None, None, None, i > 0,
-                        col_base, ncols, hv, heavy_min)
+                spmm(out32, x, srp, sci, None, None, None, i > 0,
+                     col_base, ncols, hv, heavy_min)
     if out is not None:
         return out
     if x.dtype == torch.bfloat16 and D % 8 == 0:
@@ -250,6 +275,71 @@ class _SpMM(torch.autograd.Function):
             dx = ref.spmm(yin, t_rowptr, t_colidx, ctx.num_ext)
             if deg_src is not None:
                 dx = dx * deg_src.unsqueeze(1).to(dx.dtype)
+        return (dx,) + (None,) * 17
+
+
+def quantize_rows_fp8(x, pre_scale=None):
+    """(q, s): the rows of bf16 x, times the fp32 row factor pre_scale if
+    given, as e4m3 bytes (uint8 [N, D]) and one power-of-two fp32 scale per
+    row, so that x[r] * pre_scale[r] ~= s[r] * decode(q[r]) to one e4m3
+    rounding per element. D must be a multiple of 16, at most 1024. GPU:
+    spmm_fp8.hip, no host read and no sync; CPU: ops.reference, the same
+    bits."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError("quantize_rows_fp8: x must be a bf16 [N, D] matrix, "
+                         f"got {x.dtype} {tuple(x.shape)}")
+    if x.shape[1] % 16 != 0 or not 16 <= x.shape[1] <= 1024:
+        raise ValueError("quantize_rows_fp8: D must be a multiple of 16 in "
+                         f"[16, 1024], got {x.shape[1]}")
+    if not _hip(x):
+        return ref.quantize_rows_fp8(x, pre_scale)
+    x = x.contiguous()
+    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    s = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    _C.quantize_rows_fp8(q, s, x, pre_scale)
+    return q, s
+
+
+def _spmm_fp8(x, pre_scale, rowptr, colidx, num_rows, row_scale, row_order,
+              strips, heavy, heavy_min, order):
+    """diag(row_scale) A diag(pre_scale) x with the rows of x gathered as
+    e4m3: quantise (pre_scale folded in), then the fp8 SpMM on the strip
+    plan if there is one, else the one-pass kernel. bf16 in, bf16 out."""
+    q, s = quantize_rows_fp8(x, pre_scale)
+    if not _hip(x):
+        return ref.spmm_fp8(q, s, rowptr, colidx, num_rows, row_scale)
+    if strips is not None and not _phase_cols():
+        return _strip_spmm(q, strips, num_rows, row_scale, heavy, heavy_min,
+                           order, fp8_scale=s)
+    out = torch.empty(num_rows, x.shape[1], dtype=torch.bfloat16,
+                      device=x.device)
+    _C.spmm_fp8(out, q, s, rowptr, colidx, row_scale, row_order)
+    return out
+
+
+class _SpMMFp8(torch.autograd.Function):
+    """_SpMM with every gathered row in e4m3 (gather_dtype="fp8"): the
+    forward quantises x (deg_src folded into the quantiser), the backward
+    quantises dy (deg_dst folded in) and is straight-through in x. The other
+    degree factor is applied in fp32 at the store. Same arguments as _SpMM."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, num_rows, num_ext,
+                deg_dst, deg_src, row_order, t_row_order,
+                fwd_strips=None, bwd_strips=None, fwd_heavy=None,
+                bwd_heavy=None, heavy_min=0, fwd_order=None, bwd_order=None):
+        ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src, t_row_order)
+        ctx.num_ext = num_ext
+        ctx.bwd_plan = (bwd_strips, bwd_heavy, heavy_min, bwd_order)
+        return _spmm_fp8(x, deg_src, rowptr, colidx, num_rows, deg_dst,
+                         row_order, fwd_strips, fwd_heavy, heavy_min,
+                         fwd_order)
+
+    @staticmethod
+    def backward(ctx, dy):
+        t_rowptr, t_colidx, deg_dst, deg_src, t_row_order = ctx.saved_tensors
+        dx = _spmm_fp8(dy.contiguous(), deg_dst, t_rowptr, t_colidx,
+                       ctx.num_ext, deg_src, t_row_order, *ctx.bwd_plan)
         return (dx,) + (None,) * 17
 
 
@@ -436,7 +526,7 @@ def attention_softmax(s_src, s_dst, shard, slope: float = 0.2):
 
 
 def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
-                   src_scale=None):
+                   src_scale=None, gather_dtype=None):
     """Neighbor sum-aggregation over the shard's local CSR.
 
     x: [n_ext, D] halo-extended features. Returns [n_local, D].
@@ -446,10 +536,34 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
     dst_scale/src_scale: explicit per-row fp32 factors. The fast GCN path
     pre-scales sources in the linear epilogue and passes only dst_scale
     here (saves one gather per edge).
+    gather_dtype="fp8" gathers every row as OCP e4m3 with one power-of-two
+    scale per row (spmm_fp8.hip): half the bytes per gathered row, fp32
+    accumulation, one e4m3 rounding per gathered element, in the forward
+    (x) and in the backward (dy, straight-through in x). It needs bf16 x
+    with D % 16 == 0, D <= 1024, and raises otherwise. The default,
+    shard.gather_dtype, is a preference instead: a call whose x is not bf16
+    or whose width does not qualify runs the bf16 path. Measured on the
+    Reddit shape (profiles/r46) it is no faster: D = 256 forward +10%,
+    forward + backward even; D = 64 loses clearly (4.1 against 2.1 ms
+    forward). It is opt-in; docs/KERNELS.md, spmm_fp8, has the table.
     """
     deg_dst = shard.rsqrt_deg_local if normalize else dst_scale
     deg_src = shard.rsqrt_deg_ext if normalize else src_scale
-    return _SpMM.apply(
+    fits = (x.dtype == torch.bfloat16 and x.dim() == 2
+            and x.shape[1] % 16 == 0 and 16 <= x.shape[1] <= 1024)
+    if gather_dtype is None:
+        gather_dtype = getattr(shard, "gather_dtype", None)
+        if gather_dtype == "fp8" and not fits:
+            gather_dtype = None
+    if gather_dtype not in (None, "bf16", "fp8"):
+        raise ValueError("scatter_gather: gather_dtype must be None, 'bf16' "
+                         f"or 'fp8', got {gather_dtype!r}")
+    if gather_dtype == "fp8" and not fits:
+        raise ValueError(
+            "scatter_gather: gather_dtype='fp8' needs bf16 x with D % 16 == 0 "
+            f"and D <= 1024, got {x.dtype} {tuple(x.shape)}")
+    op = _SpMMFp8 if gather_dtype == "fp8" else _SpMM
+    return op.apply(
         x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
         shard.n_local, shard.n_ext, deg_dst, deg_src,
         shard.row_order, shard.t_row_order,

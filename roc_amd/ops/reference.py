@@ -27,6 +27,52 @@ def spmm(x: torch.Tensor, rowptr: torch.Tensor, colidx: torch.Tensor,
     return out
 
 
+FP8_MAX = 448.0     # largest e4m3 (OCP, torch.float8_e4m3fn) value
+FP8_MIN_EXP = -100  # floor of the row scale's exponent (spmm_fp8.hip)
+
+
+def quantize_rows_fp8(x: torch.Tensor, pre_scale=None):
+    """(q uint8 [N, D], s fp32 [N]) — the bit-exact definition of the GPU
+    quantiser (spmm_fp8.hip). y = x * pre_scale in one fp32 multiply;
+    s = 2^k with k the smallest integer such that max|y| <= 448 * 2^k
+    (k >= FP8_MIN_EXP; s = 1 for an all-zero row); q = RNE_e4m3(y / s), the
+    division an exact exponent shift. NaN / inf are out of contract."""
+    y = x.float()
+    if pre_scale is not None:
+        y = y * pre_scale.float().unsqueeze(1)
+    amax = y.abs().amax(dim=1)
+    m, e = torch.frexp(amax)  # amax = m * 2^e, m in [0.5, 1); 448 = .875 * 2^9
+    k = torch.where(m <= 0.875, e - 9, e - 8).clamp(min=FP8_MIN_EXP)
+    k = torch.where(amax == 0, torch.zeros_like(k), k)
+    s = torch.ldexp(torch.ones_like(amax), k)
+    z = torch.ldexp(y, -k.unsqueeze(1)).clamp(-FP8_MAX, FP8_MAX)
+    return z.to(torch.float8_e4m3fn).view(torch.uint8), s
+
+
+def dequantize_rows_fp8(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """fp32 s[r] * decode(q[r, :]); exact, s being a power of two."""
+    return q.view(torch.float8_e4m3fn).float() * s.unsqueeze(1)
+
+
+def spmm_fp8(q: torch.Tensor, s: torch.Tensor, rowptr: torch.Tensor,
+             colidx: torch.Tensor, num_rows: int, deg_dst=None,
+             out_dtype=torch.bfloat16) -> torch.Tensor:
+    """out[v] = deg_dst[v] * sum_e s[u_e] * decode(q[u_e]) as the GPU kernel
+    computes it: a sequential fp32 sum in ascending edge order (pass k adds
+    edge k of every row that has one), one fp32 multiply by deg_dst, one
+    cast."""
+    x = dequantize_rows_fp8(q, s)
+    deg = rowptr[1:] - rowptr[:-1]
+    out = torch.zeros(num_rows, q.shape[1], dtype=torch.float32,
+                      device=q.device)
+    for k in range(int(deg.max()) if num_rows and colidx.numel() else 0):
+        rows = (deg > k).nonzero().squeeze(1)
+        out[rows] += x[colidx[rowptr[rows] + k].long()]
+    if deg_dst is not None:
+        out = out * deg_dst.float().unsqueeze(1)
+    return out.to(out_dtype)
+
+
 def spmm_weighted(x: torch.Tensor, rowptr: torch.Tensor,
                   colidx: torch.Tensor, edge_val: torch.Tensor,
                   num_rows: int) -> torch.Tensor:

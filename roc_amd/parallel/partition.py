@@ -114,6 +114,10 @@ class GraphShard:
     # heavy lists. None = natural plan.
     fwd_strip_order: Optional[list] = None
     bwd_strip_order: Optional[list] = None
+    # how ops.functional.scatter_gather gathers feature rows by default:
+    # None / "bf16" = as stored, "fp8" = e4m3 rows with per-row scales
+    # (world size 1 only; engine.Trainer sets it)
+    gather_dtype: Optional[str] = None
 
     def to(self, device) -> "GraphShard":
         d = {}

@@ -3,6 +3,7 @@
 rounds per CDNA guide §5.4 rule 24). Run on a GPU box:
 
   python scripts/bench_spmm.py [--nodes N --edges E --rounds R]
+  python scripts/bench_spmm.py --fp8 --dims 256 64   # bf16 vs e4m3 gather
 """
 import argparse
 import os
@@ -29,18 +30,63 @@ def time_variant(fn, rounds, stream=None):
     return times[len(times) // 2], times[0]
 
 
+def bench_fp8(args, g):
+    """scatter_gather as the shard ships it (its strip plan, dst scale):
+    bf16 rows against quantise + e4m3 rows, forward and forward + backward,
+    and the quantiser alone. Same rounds, one process, interleaved by D."""
+    from roc_amd.ops import functional as F
+    from roc_amd.parallel.partition import build_shard
+
+    dev = "cuda:0"
+    sh = build_shard(g, 0, 1).to(dev)
+    print(f"plan: strips={None if sh.fwd_strips is None else len(sh.fwd_strips)}"
+          f" ordered={sh.fwd_strip_order is not None}"
+          f" heavy={sh.fwd_strip_heavy is not None}"
+          f" row_order={sh.row_order is not None}")
+    for D in args.dims:
+        x = torch.randn(g.num_nodes, D).to(torch.bfloat16).to(dev)
+        gy = torch.randn(g.num_nodes, D).to(torch.bfloat16).to(dev)
+        print(f"== D={D} ==")
+
+        def fwd(mode, x=x):
+            return F.scatter_gather(x, sh, dst_scale=sh.rsqrt_deg_local,
+                                    gather_dtype=mode)
+
+        def fwd_bwd(mode):
+            xl = x.detach().requires_grad_(True)
+            torch.autograd.grad(fwd(mode, xl), xl, gy)
+
+        rows = [("quantise", lambda: F.quantize_rows_fp8(x))]
+        for mode in ("bf16", "fp8"):
+            rows.append((f"{mode} fwd", lambda m=mode: fwd(m)))
+            rows.append((f"{mode} fwd+bwd", lambda m=mode: fwd_bwd(m)))
+        for name, fn in rows:
+            med, best = time_variant(fn, args.rounds)
+            print(f"  {name:12s}: median {med:8.3f} ms  best {best:8.3f}",
+                  flush=True)
+        rel = (fwd("fp8").float() - fwd("bf16").float()).norm() / \
+            fwd("bf16").float().norm()
+        print(f"  fp8 vs bf16 result: relative L2 difference {rel:.4f}")
+    print("done")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=232965)
     ap.add_argument("--edges", type=int, default=114848857)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--dims", type=int, nargs="+", default=[48, 256])
+    ap.add_argument("--fp8", action="store_true",
+                    help="bf16 vs e4m3 row gather through scatter_gather on "
+                         "the shard's shipped plan (instead of the A/B sweep)")
     args = ap.parse_args()
 
     from roc_amd.graph import synthetic_graph
     from roc_amd import _C
 
     g = synthetic_graph(args.nodes, args.edges, seed=1)
+    if args.fp8:
+        return bench_fp8(args, g)
     dev = "cuda:0"
     rowptr = g.rowptr.to(dev)
     colidx = g.colidx.to(dev)

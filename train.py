@@ -63,6 +63,11 @@ def parse_args():
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dtype", default="auto", choices=["auto", "bf16", "fp32"])
+    ap.add_argument("--gather-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="how the sum aggregations gather feature rows: "
+                         "fp8 = e4m3 rows with per-row power-of-two scales "
+                         "(bf16 compute, layer widths that are a multiple "
+                         "of 16, one process)")
     ap.add_argument("--loss", default="mean", choices=["mean", "sum"],
                     help="sum replicates the reference's unscaled gradient")
     ap.add_argument("--eval-every", type=int, default=5)
@@ -154,6 +159,9 @@ def parse_args():
     if args.aggr != "mean" and args.model != "sage":
         ap.error(f"--aggr {args.aggr} needs --model sage: --model "
                  f"{args.model} has a fixed aggregation")
+    if args.gather_dtype not in ("bf16", "fp8"):  # a YAML value
+        ap.error(f"--gather-dtype must be bf16 or fp8, got "
+                 f"{args.gather_dtype!r}")
     if args.norm not in ("none", "layer"):  # a YAML value
         ap.error(f"--norm must be none or layer, got {args.norm!r}")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
@@ -334,7 +342,8 @@ def main():
     trainer = Trainer(model, shard, feats, labels, mask, opt, device=device,
                       compute_dtype=dtype, grad_scale=gs, seed=args.seed,
                       num_classes=num_classes if dims[-1] != num_classes
-                      else None, local_slices=pre_shard is not None)
+                      else None, local_slices=pre_shard is not None,
+                      gather_dtype=args.gather_dtype)
     trainer.clip_norm = args.clip_norm
     if args.trace:
         trainer.enable_tracing()
