@@ -18,6 +18,15 @@ void spmm_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor scale,
               c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
               c10::optional<torch::Tensor> final_out,
               c10::optional<torch::Tensor> out_rows);
+void spmm_drop(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
+               torch::Tensor colidx, double p, int64_t seed, int64_t offset,
+               c10::optional<torch::Tensor> counter,
+               c10::optional<torch::Tensor> row_scale,
+               c10::optional<torch::Tensor> row_order, bool transposed);
+void drop_edge_mask(torch::Tensor out, torch::Tensor rowptr,
+                    torch::Tensor colidx, double p, int64_t seed,
+                    int64_t offset, c10::optional<torch::Tensor> counter,
+                    bool transposed);
 void rowscale(torch::Tensor out, torch::Tensor x, torch::Tensor scale);
 void cast_rowscale(torch::Tensor out, torch::Tensor x,
                    c10::optional<torch::Tensor> scale);
@@ -149,6 +158,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("heavy_min") = 0,
         pybind11::arg("final_out") = pybind11::none(),
         pybind11::arg("out_rows") = pybind11::none());
+  m.def("spmm_drop", &spmm_drop,
+        "DropEdge CSR SpMM: out = row_scale / (1 - p) * sum over the kept "
+        "edges; the mask is a function of (seed, offset, counter, row, col). "
+        "transposed = the CSR is the transpose: the same mask, roles swapped",
+        pybind11::arg("out"), pybind11::arg("x"), pybind11::arg("rowptr"),
+        pybind11::arg("colidx"), pybind11::arg("p"), pybind11::arg("seed"),
+        pybind11::arg("offset"), pybind11::arg("counter") = pybind11::none(),
+        pybind11::arg("row_scale") = pybind11::none(),
+        pybind11::arg("row_order") = pybind11::none(),
+        pybind11::arg("transposed") = false);
+  m.def("drop_edge_mask", &drop_edge_mask,
+        "the DropEdge keep mask of a CSR, uint8 [E] in its edge order",
+        pybind11::arg("out"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("p"), pybind11::arg("seed"), pybind11::arg("offset"),
+        pybind11::arg("counter") = pybind11::none(),
+        pybind11::arg("transposed") = false);
   m.def("rowscale", &rowscale);
   m.def("cast_rowscale", &cast_rowscale,
         "fp32 -> bf16 cast with optional row scale (strip epilogue)",

@@ -3,6 +3,10 @@
 Mirrors the reference driver's model (`gnn.cc:66-92`): per layer
   dropout -> linear -> indegree_norm -> scatter_gather -> indegree_norm
   -> relu (not on last layer) [-> residual projection + add]
+edge_drop=p is DropEdge: in training every aggregation drops each edge with
+probability p and scales the rest by 1 / (1 - p), a fresh stateless mask per
+layer and epoch (ops.functional.scatter_gather); the D^-1/2 factors stay
+those of the full graph.
 norm="layer" replaces that relu with a fused per-node LayerNorm + ReLU
 (before the residual add); see models/norm.py.
 The two indegree_norms around the aggregation implement the symmetric
@@ -37,9 +41,10 @@ _ADAPTIVE = None
 class GCN(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
                  residual: bool = False, fused_norm: bool = True,
-                 norm: str = "none"):
+                 norm: str = "none", edge_drop: float = 0.0):
         super().__init__()
         self.norm = norm
+        self.edge_drop = float(edge_drop)
         self.dims = list(dims)
         self.p = float(dropout)
         self.residual = residual
@@ -66,6 +71,8 @@ class GCN(torch.nn.Module):
 
     def _layer(self, i, x, shard, group):
         w = self.weights[i]
+        drop = dict(edge_drop=self.edge_drop, training=self.training,
+                    edge_call_id=i)
         h = F.dropout(x, self.p, self.training, call_id=i)
         if self.fused_norm:
             if w.shape[0] < w.shape[1] and _adaptive_agg():
@@ -75,7 +82,7 @@ class GCN(torch.nn.Module):
                 # in_dim-wide rows instead of out_dim-wide ones
                 h = F.degree_scale(h, shard.rsqrt_deg_local)
                 h = aggregate(h, shard, dst_scale=shard.rsqrt_deg_local,
-                              group=group)
+                              group=group, **drop)
                 h = F.linear(h, w)
             else:
                 # source-side D^-1/2 rides the GEMM epilogue (owner
@@ -86,12 +93,13 @@ class GCN(torch.nn.Module):
                 # strategy (halo a2a / overlap / all_gather) is the
                 # shard's choice — see parallel/aggregate.py
                 h = aggregate(h, shard, dst_scale=shard.rsqrt_deg_local,
-                              group=group)
+                              group=group, **drop)
         else:
             h = F.linear(h, w)
             h = halo_exchange(h, shard, group)
             h = F.indegree_norm(
-                F.scatter_gather(F.degree_scale(h, shard.rsqrt_deg_ext), shard),
+                F.scatter_gather(F.degree_scale(h, shard.rsqrt_deg_ext), shard,
+                                 **drop),
                 shard)
         if i < len(self.weights) - 1:
             h = hidden_act(self, i, h)

@@ -2,6 +2,8 @@
 
 h' = MLP( (1 + eps) * h_v + sum_{u in N(v)} h_u ),  eps learnable.
 Exercises the scatter-add aggregation path (BASELINE.json config #4).
+edge_drop=p is DropEdge: in training the sum drops each edge with probability
+p and scales the rest by 1 / (1 - p) (ops.functional.scatter_gather).
 norm="layer" replaces the relu after the MLP's second linear with a fused
 per-node LayerNorm + ReLU on the hidden layers; see models/norm.py.
 """
@@ -17,9 +19,11 @@ from .norm import make_norm_params, hidden_act, norm_parameters
 
 class GIN(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
-                 mlp_hidden: int = 0, norm: str = "none"):
+                 mlp_hidden: int = 0, norm: str = "none",
+                 edge_drop: float = 0.0):
         super().__init__()
         self.norm = norm
+        self.edge_drop = float(edge_drop)
         self.dims = list(dims)
         self.p = float(dropout)
         self.eps = torch.nn.ParameterList()
@@ -40,7 +44,8 @@ class GIN(torch.nn.Module):
 
     def _layer(self, i, x, shard, group):
         h = F.dropout(x, self.p, self.training, call_id=i)
-        agg = aggregate(h, shard, group=group)
+        agg = aggregate(h, shard, group=group, edge_drop=self.edge_drop,
+                        training=self.training, edge_call_id=i)
         h = agg + (1.0 + self.eps[i]).to(h.dtype) * h  # scalar-eps glue
         h = F.linear(h, self.w1[i], activation="relu")
         h = F.linear(h, self.w2[i])

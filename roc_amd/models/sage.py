@@ -17,6 +17,10 @@ h' = relu( W_self·h_v  +  W_neigh·ext_{u in N(v)} h_u )
 An extremum does not commute with W_neigh, so that layer always
 aggregates first, at the input width, and ROC_ADAPTIVE_AGG does not apply.
 
+edge_drop=p (mean aggregation, full-graph path) is DropEdge: in training each
+edge is dropped with probability p and the kept sum is scaled by 1 / (1 - p)
+before the 1/deg of the full graph (ops.functional.scatter_gather).
+
 norm="layer" replaces the hidden layers' relu with a fused per-node
 LayerNorm + ReLU, on the full-graph and the sampled path alike; see
 models/norm.py.
@@ -33,9 +37,14 @@ from .norm import make_norm_params, hidden_act, norm_parameters
 
 class GraphSAGE(torch.nn.Module):
     def __init__(self, dims, dropout: float = 0.5, seed: int = 1,
-                 aggr: str = "mean", norm: str = "none"):
+                 aggr: str = "mean", norm: str = "none",
+                 edge_drop: float = 0.0):
         super().__init__()
         self.norm = norm
+        self.edge_drop = float(edge_drop)
+        if edge_drop and aggr != "mean":
+            raise ValueError("edge_drop needs aggr='mean': the max / min "
+                             "aggregations have no DropEdge kernel")
         if aggr not in ("mean", "max", "min"):
             raise ValueError(
                 f"aggr must be 'mean', 'max' or 'min', got {aggr!r}")
@@ -70,6 +79,8 @@ class GraphSAGE(torch.nn.Module):
         h_self = F.linear(h, self.w_self[i])
         wn = self.w_neigh[i]
         from .gcn import _adaptive_agg
+        drop = dict(edge_drop=self.edge_drop, training=self.training,
+                    edge_call_id=i)
         if self.aggr != "mean":
             hn = aggregate(h, shard, group=group, reduce=self.aggr)
             hn = F.linear(hn, wn)
@@ -78,12 +89,12 @@ class GraphSAGE(torch.nn.Module):
             # input width (mean_u(h W) == (mean_u h) W) — smaller
             # gather stream and halo exchange
             hn = aggregate(h, shard, dst_scale=shard.inv_deg_local,
-                           group=group)
+                           group=group, **drop)
             hn = F.linear(hn, wn)
         else:
             hn = F.linear(h, wn)
             hn = aggregate(hn, shard, dst_scale=shard.inv_deg_local,
-                           group=group)  # fused mean
+                           group=group, **drop)  # fused mean
         h = F.add(h_self, hn)
         if i < len(self.w_self) - 1:
             h = hidden_act(self, i, h)

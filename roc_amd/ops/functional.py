@@ -343,6 +343,84 @@ class _SpMMFp8(torch.autograd.Function):
         return (dx,) + (None,) * 17
 
 
+def _edge_call_offset(call_id):
+    """(seed, offset, counter) of one mask draw, taken from the dropout
+    state exactly as _Dropout takes them: a call_id gives a stable per-epoch
+    offset (identical on a recompute re-forward; the epoch comes from the
+    device counter under hipGraph, else from the host), no call_id takes
+    the running offset."""
+    counter = _DROPOUT_STATE["counter"]
+    if call_id is not None:
+        offset = int(call_id)
+        if counter is None:
+            offset += _DROPOUT_STATE["epoch"] * 65536
+    else:
+        offset = _DROPOUT_STATE["offset"]
+        _DROPOUT_STATE["offset"] += 1
+    return _DROPOUT_STATE["seed"], offset, counter
+
+
+def _spmm_drop(x, rowptr, colidx, num_rows, pre_scale, row_scale, row_order,
+               p, seed, offset, counter, transposed):
+    """diag(row_scale) / (1 - p) * (A o mask) diag(pre_scale) x over one CSR
+    (transposed: the transpose CSR, the same mask). GPU: one rowscale pass
+    for pre_scale, then spmm_drop.hip; CPU: the reference mask and spmm."""
+    if _hip(x):
+        x = x.contiguous()
+        if pre_scale is not None:
+            tmp = torch.empty_like(x)
+            _C.rowscale(tmp, x, pre_scale)
+            x = tmp
+        out = torch.empty(num_rows, x.shape[1], dtype=x.dtype, device=x.device)
+        _C.spmm_drop(out, x, rowptr, colidx, p, seed, offset, counter,
+                     row_scale, row_order, transposed)
+        return out
+    if counter is not None:
+        offset += int(counter.item()) * 65536
+    keep = ref.drop_edge_mask(rowptr, colidx, p, seed, offset, transposed)
+    if pre_scale is not None:
+        x = x * pre_scale.unsqueeze(1).to(x.dtype)
+    out = ref.spmm_weighted(x, rowptr, colidx, keep.to(x.dtype), num_rows)
+    if row_scale is not None:
+        out = out * row_scale.unsqueeze(1).to(out.dtype)
+    return out * (1.0 / (1.0 - p))
+
+
+class _SpMMDrop(torch.autograd.Function):
+    """_SpMM over the edges a stateless DropEdge mask keeps, scaled by
+    1 / (1 - p). The mask is a pure function of (seed, offset, counter, v, u)
+    (spmm_drop.hip), so nothing is stored: the backward runs the same kernel
+    on the transpose CSR and draws the same mask with the roles swapped."""
+
+    @staticmethod
+    def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, num_rows, num_ext,
+                deg_dst, deg_src, row_order, t_row_order, p, call_id):
+        ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src, t_row_order)
+        ctx.num_ext = num_ext
+        ctx.draw = (p,) + _edge_call_offset(call_id)
+        return _spmm_drop(x, rowptr, colidx, num_rows, deg_src, deg_dst,
+                          row_order, *ctx.draw, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        t_rowptr, t_colidx, deg_dst, deg_src, t_row_order = ctx.saved_tensors
+        dx = _spmm_drop(dy.contiguous(), t_rowptr, t_colidx, ctx.num_ext,
+                        deg_dst, deg_src, t_row_order, *ctx.draw, True)
+        return (dx,) + (None,) * 12
+
+
+def scatter_gather_drop_csr(x, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                            num_ext, p, dst_scale=None, src_scale=None,
+                            row_order=None, t_row_order=None, call_id=None):
+    """_SpMMDrop over an explicit CSR pair (parallel.aggregate runs it over
+    the gather-space CSR of allgather mode)."""
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"edge_drop must be in (0, 1), got {p}")
+    return _SpMMDrop.apply(x, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                           num_ext, dst_scale, src_scale, row_order,
+                           t_row_order, float(p), call_id)
+
+
 class _SpMMEdge(torch.autograd.Function):
     """out[v] = sum_{e in row v} w[e] * x[col_e]  (+ optional dst row
     scale). The edge-tensor consumer op: w is a per-local-edge tensor
@@ -526,7 +604,8 @@ def attention_softmax(s_src, s_dst, shard, slope: float = 0.2):
 
 
 def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
-                   src_scale=None, gather_dtype=None):
+                   src_scale=None, gather_dtype=None, edge_drop: float = 0.0,
+                   training: bool = False, edge_call_id=None):
     """Neighbor sum-aggregation over the shard's local CSR.
 
     x: [n_ext, D] halo-extended features. Returns [n_local, D].
@@ -546,9 +625,30 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
     Reddit shape (profiles/r46) it is no faster: D = 256 forward +10%,
     forward + backward even; D = 64 loses clearly (4.1 against 2.1 ms
     forward). It is opt-in; docs/KERNELS.md, spmm_fp8, has the table.
+    edge_drop=p with training=True is DropEdge (Rong et al., ICLR 2020): each
+    edge is dropped with probability p by a stateless mask drawn inside the
+    gather kernel (spmm_drop.hip), and the sum over the kept edges is scaled
+    by 1 / (1 - p); the degree factors stay those of the full graph. The mask
+    takes seed, epoch and device counter from the dropout state as
+    dropout() does, with edge_call_id in the place of call_id (the models
+    pass the layer index), so it is identical on a recompute re-forward and
+    fresh on every epoch and hipGraph replay; the backward redraws it.
+    edge_drop == 0 or training false is the undropped path, untouched. The
+    drop path always runs its one-pass kernel on the full CSR: strip plans
+    are not used with it (a strip plan of the drop kernel is the follow-up),
+    and it does not combine with gather_dtype="fp8" (raises; a shard-level
+    fp8 preference gives way). docs/KERNELS.md, spmm_drop, has the numbers.
     """
     deg_dst = shard.rsqrt_deg_local if normalize else dst_scale
     deg_src = shard.rsqrt_deg_ext if normalize else src_scale
+    if training and edge_drop > 0.0:
+        if gather_dtype == "fp8":
+            raise ValueError("scatter_gather: edge_drop > 0 does not combine "
+                             "with gather_dtype='fp8'")
+        return scatter_gather_drop_csr(
+            x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+            shard.n_local, shard.n_ext, edge_drop, deg_dst, deg_src,
+            shard.row_order, shard.t_row_order, edge_call_id)
     fits = (x.dtype == torch.bfloat16 and x.dim() == 2
             and x.shape[1] % 16 == 0 and 16 <= x.shape[1] <= 1024)
     if gather_dtype is None:

@@ -382,6 +382,64 @@ def dropout_mask(shape, p: float, seed: int, offset: int, device) -> torch.Tenso
     return (torch.rand(shape, generator=gen) >= p).to(device)
 
 
+PHILOX_FEATURE_STREAM = 0x9E3779B9  # csrc/philox.h: dropout.hip
+PHILOX_EDGE_STREAM = 0x7F4A7C15     # csrc/philox.h: spmm_drop.hip
+
+
+def philox4x32_10(idx, offset: int, seed: int,
+                  stream: int = PHILOX_EDGE_STREAM):
+    """Philox4x32-10 as csrc/philox.h computes it, in integer arithmetic:
+    counter (idx lo, idx hi, offset, stream), key (seed lo, seed hi). idx is
+    an array-like of 64-bit counters; returns a uint32 numpy array
+    [len(idx), 4], the four output words of each."""
+    import numpy as np
+    idx = np.asarray(idx).astype(np.uint64).reshape(-1)
+    m32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    c0, c1 = idx & m32, idx >> s32
+    c2 = np.full_like(c0, int(offset) & 0xFFFFFFFF)
+    c3 = np.full_like(c0, int(stream) & 0xFFFFFFFF)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2  # 32 x 32 bits: exact in uint64
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0 = (k0 + 0x9E3779B9) & 0xFFFFFFFF
+        k1 = (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
+
+
+def drop_edge_thresh(p: float) -> int:
+    """The integer a draw is compared with: min(floor(p * 2^32), 2^32 - 1)."""
+    import math
+    return min(math.floor(float(p) * 4294967296.0), 0xFFFFFFFF)
+
+
+def drop_edge_mask(rowptr: torch.Tensor, colidx: torch.Tensor, p: float,
+                   seed: int, offset: int,
+                   transposed: bool = False) -> torch.Tensor:
+    """The DropEdge keep mask of a CSR, bool [E] in its edge order, bit for
+    bit the mask of csrc/spmm_drop.hip: edge (v <- u) is kept iff
+    philox4x32_10((v << 32) | u, offset, seed).x >= drop_edge_thresh(p), v the
+    row and u the column of the forward CSR. transposed=True says the CSR
+    given is the transpose (rows are sources): the same function with the
+    roles swapped, so no edge permutation is involved. `offset` is the
+    effective one (counter * 65536 + offset where a device counter is in
+    use), taken modulo 2^32."""
+    import numpy as np
+    rp = rowptr.cpu().numpy().astype(np.int64)
+    row = np.repeat(np.arange(rp.size - 1, dtype=np.uint64),
+                    np.diff(rp)).astype(np.uint64)
+    col = colidx.cpu().numpy().astype(np.int64).astype(np.uint64)
+    v, u = (col, row) if transposed else (row, col)
+    draw = philox4x32_10((v << np.uint64(32)) | (u & np.uint64(0xFFFFFFFF)),
+                         offset, seed)[:, 0]
+    keep = draw.astype(np.uint64) >= np.uint64(drop_edge_thresh(p))
+    return torch.from_numpy(keep).to(colidx.device)
+
+
 def softmax_cross_entropy(
     logits: torch.Tensor,
     labels: torch.Tensor,

@@ -218,7 +218,30 @@ def _aggregate_reduce(x, shard, reduce, group):
     return local(halo_exchange(x, shard, group))
 
 
-def aggregate(x, shard, dst_scale=None, group=None, reduce="sum"):
+def _aggregate_drop(x, shard, dst_scale, group, p, call_id):
+    """DropEdge sum aggregation of the local block (ops.functional,
+    _SpMMDrop). Like _aggregate_reduce, the exchange completes before the
+    local op starts; there is no comm/compute-overlap variant."""
+    from ..ops import functional as Fn
+    if shard.world_size > 1 and shard.comm_mode == "allgather":
+        gathered = _GatherBlocks.apply(x, shard, group)
+        cuda = x.is_cuda
+        return Fn.scatter_gather_drop_csr(
+            gathered, shard.rowptr, shard.ag_colidx, shard.ag_t_rowptr,
+            shard.ag_t_colidx, shard.n_local,
+            shard.world_size * shard.ag_max_rows, p, dst_scale=dst_scale,
+            row_order=shard.row_order if cuda else None,
+            t_row_order=shard.ag_t_row_order if cuda else None,
+            call_id=call_id)
+    if shard.world_size > 1:
+        x = halo_exchange(x, shard, group)
+    return Fn.scatter_gather(x, shard, dst_scale=dst_scale, edge_drop=p,
+                             training=True, edge_call_id=call_id)
+
+
+def aggregate(x, shard, dst_scale=None, group=None, reduce="sum",
+              edge_drop: float = 0.0, training: bool = False,
+              edge_call_id=None):
     """Distributed neighbor aggregation of the LOCAL feature block.
     Returns [n_local, D]. reduce="sum" (+ optional fused dst-side degree
     scale) is the sum / mean path; reduce="max" | "min" takes the
@@ -227,8 +250,17 @@ def aggregate(x, shard, dst_scale=None, group=None, reduce="sum"):
     reduce="stats" returns [n_local, 4*D], the PNA aggregators
     [mean | std | max | min] (ops.functional.scatter_gather_stats).
     Neither takes a dst_scale. They exchange first and aggregate after, in
-    every comm mode: they have no comm/compute-overlap variant yet."""
+    every comm mode: they have no comm/compute-overlap variant yet.
+    edge_drop=p with training=True (reduce="sum" only) is DropEdge, see
+    ops.functional.scatter_gather; it too exchanges first and aggregates
+    after, over the local ids of the shard (the gather-space ids in
+    allgather mode), so every partitioning draws its own mask."""
     from ..ops import functional as Fn
+    if training and edge_drop > 0.0:
+        if reduce != "sum":
+            raise ValueError("edge_drop applies to reduce='sum' only")
+        return _aggregate_drop(x, shard, dst_scale, group, edge_drop,
+                               edge_call_id)
     if reduce != "sum":
         if dst_scale is not None:
             raise ValueError("dst_scale applies to reduce='sum' only")

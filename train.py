@@ -10,7 +10,8 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer, --dtype,
+--model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer,
+--edge-drop P, --dtype,
 --checkpoint/--resume, --trace.
 """
 import argparse
@@ -61,6 +62,11 @@ def parse_args():
     ap.add_argument("--decay-rate", type=float, default=0.97)
     ap.add_argument("--decay-steps", type=int, default=100)
     ap.add_argument("--dropout", type=float, default=0.5)
+    ap.add_argument("--edge-drop", type=float, default=0.0,
+                    help="DropEdge probability of --model gcn, sage (mean) "
+                         "or gin: each training aggregation drops every edge "
+                         "with this probability (a fresh stateless mask per "
+                         "layer and epoch) and scales the rest by 1/(1-p)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dtype", default="auto", choices=["auto", "bf16", "fp32"])
     ap.add_argument("--gather-dtype", default="bf16", choices=["bf16", "fp8"],
@@ -162,6 +168,14 @@ def parse_args():
     if args.gather_dtype not in ("bf16", "fp8"):  # a YAML value
         ap.error(f"--gather-dtype must be bf16 or fp8, got "
                  f"{args.gather_dtype!r}")
+    if not 0.0 <= float(args.edge_drop) < 1.0:
+        ap.error(f"--edge-drop must be in [0, 1), got {args.edge_drop!r}")
+    if args.edge_drop and (args.model not in ("gcn", "sage", "gin")
+                           or args.aggr != "mean" or args.sample):
+        ap.error("--edge-drop needs the full-graph --model gcn, sage "
+                 "(--aggr mean) or gin")
+    if args.edge_drop and args.gather_dtype == "fp8":
+        ap.error("--edge-drop does not combine with --gather-dtype fp8")
     if args.norm not in ("none", "layer"):  # a YAML value
         ap.error(f"--norm must be none or layer, got {args.norm!r}")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
@@ -277,6 +291,8 @@ def main():
             mkw["k"] = args.k_hops
     if args.norm != "none":
         mkw["norm"] = args.norm
+    if args.edge_drop:
+        mkw["edge_drop"] = float(args.edge_drop)
     model = build_model(args.model, dims, dropout=args.dropout,
                         seed=args.seed, **mkw)
     if args.recompute:
