@@ -80,6 +80,26 @@ void layer_norm_bwd(torch::Tensor dx, torch::Tensor dgamma,
                     torch::Tensor dbeta, torch::Tensor dy, torch::Tensor x,
                     torch::Tensor mean, torch::Tensor rstd,
                     torch::Tensor gamma, torch::Tensor beta, bool relu);
+void batch_norm_stats(torch::Tensor mean, torch::Tensor m2, torch::Tensor x,
+                      int64_t depth);
+void batch_norm_finalize(torch::Tensor rstd, torch::Tensor mean,
+                         torch::Tensor m2,
+                         c10::optional<torch::Tensor> running_mean,
+                         c10::optional<torch::Tensor> running_var, double n,
+                         double momentum, double eps);
+void batch_norm_apply(torch::Tensor y, torch::Tensor x, torch::Tensor mean,
+                      torch::Tensor rstd, torch::Tensor gamma,
+                      torch::Tensor beta, bool relu);
+void batch_norm_bwd_reduce(torch::Tensor dgamma, torch::Tensor dbeta,
+                           torch::Tensor dy, torch::Tensor x,
+                           torch::Tensor mean, torch::Tensor rstd,
+                           torch::Tensor gamma, torch::Tensor beta, bool relu,
+                           int64_t depth);
+void batch_norm_bwd_dx(torch::Tensor dx, torch::Tensor dy, torch::Tensor x,
+                       torch::Tensor mean, torch::Tensor rstd,
+                       torch::Tensor gamma, torch::Tensor beta,
+                       torch::Tensor s_g, torch::Tensor s_gx, double n,
+                       bool relu);
 void graph_attn_fwd(torch::Tensor out, c10::optional<torch::Tensor> lse,
                     torch::Tensor q, torch::Tensor kv, torch::Tensor rowptr,
                     torch::Tensor colidx,
@@ -253,6 +273,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("mean"),
         pybind11::arg("rstd"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("relu") = false);
+  m.def("batch_norm_stats", &batch_norm_stats,
+        "column mean and sum of squared deviations of [N, D] (shifted sums, "
+        "order-fixed Chan merge); depth = rows in flight, 0 = default",
+        pybind11::arg("mean"), pybind11::arg("m2"), pybind11::arg("x"),
+        pybind11::arg("depth") = 0);
+  m.def("batch_norm_finalize", &batch_norm_finalize,
+        "rstd = 1/sqrt(m2/n + eps); advances the running buffers when given",
+        pybind11::arg("rstd"), pybind11::arg("mean"), pybind11::arg("m2"),
+        pybind11::arg("running_mean"), pybind11::arg("running_var"),
+        pybind11::arg("n"), pybind11::arg("momentum"), pybind11::arg("eps"));
+  m.def("batch_norm_apply", &batch_norm_apply,
+        "y = act(((x - mean) * rstd) * gamma + beta) with column statistics",
+        pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("mean"),
+        pybind11::arg("rstd"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("relu") = false);
+  m.def("batch_norm_bwd_reduce", &batch_norm_bwd_reduce,
+        "BatchNorm gradient, column sums: dgamma, dbeta (overwritten) by an "
+        "order-fixed slab fold",
+        pybind11::arg("dgamma"), pybind11::arg("dbeta"), pybind11::arg("dy"),
+        pybind11::arg("x"), pybind11::arg("mean"), pybind11::arg("rstd"),
+        pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("relu") = false, pybind11::arg("depth") = 0);
+  m.def("batch_norm_bwd_dx", &batch_norm_bwd_dx,
+        "BatchNorm gradient, dx from the global column sums s_g, s_gx and n",
+        pybind11::arg("dx"), pybind11::arg("dy"), pybind11::arg("x"),
+        pybind11::arg("mean"), pybind11::arg("rstd"), pybind11::arg("gamma"),
+        pybind11::arg("beta"), pybind11::arg("s_g"), pybind11::arg("s_gx"),
+        pybind11::arg("n"), pybind11::arg("relu") = false);
   m.def("graph_attn_fwd", &graph_attn_fwd,
         "dot-product attention over in-neighbours (online softmax); "
         "lse = None skips the log-sum-exp store",

@@ -47,53 +47,6 @@ constexpr int kBwdGridCap = 1024;
 constexpr int kFoldCols = 16;
 constexpr int kFoldSegs = kBlock / kFoldCols;
 
-// ---- one unit of a row: full = one 16-B access, straddling = guarded
-// scalar accesses, past D = zeros / nothing ---------------------------------
-__device__ __forceinline__ void load_unit(float (&v)[4], const float* p,
-                                          int nvalid) {
-  if (nvalid == 4) {
-    load_f32x4(p, v);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = j < nvalid ? p[j] : 0.f;
-  }
-}
-__device__ __forceinline__ void load_unit(float (&v)[8], const float* p,
-                                          int nvalid) {
-  if (nvalid == 8) {
-    load_f32x4(p, v);
-    load_f32x4(p + 4, v + 4);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = j < nvalid ? p[j] : 0.f;
-  }
-}
-// bf16 rows are whole units (D % 8 == 0)
-__device__ __forceinline__ void load_unit(float (&v)[8],
-                                          const unsigned short* p,
-                                          int nvalid) {
-  if (nvalid == 8) {
-    load_bf16x8(p, v);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = 0.f;
-  }
-}
-__device__ __forceinline__ void store_unit(float* p, const float (&v)[4],
-                                           int nvalid) {
-  if (nvalid == 4) {
-    store_vec(p, v);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < nvalid) p[j] = v[j];
-  }
-}
-__device__ __forceinline__ void store_unit(unsigned short* p,
-                                           const float (&v)[8], int nvalid) {
-  if (nvalid == 8) store_vec(p, v);
-}
-
 // what every kernel keeps per lane for the whole launch
 template <typename T, int TEAM, int UNITS>
 struct LaneCols {

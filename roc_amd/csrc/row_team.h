@@ -1,6 +1,6 @@
 // Row-team frame shared by the CSR kernels (spmm.hip, seg_max.hip,
 // seg_stats.hip, graph_attn.hip, edge_softmax.hip) and by the row kernels of
-// layer_norm.hip. gather.h adds the device side of the feature-row
+// layer_norm.hip and batch_norm.hip. gather.h adds the device side of the feature-row
 // gathers, csr_launch.h the host side of their launches.
 //
 // A team of TEAM contiguous lanes (a power of two <= 64, so a team never
@@ -58,4 +58,51 @@ void dispatch_team(int team, F&& f) {
     case 32: f(std::integral_constant<int, 32>{}); break;
     default: f(std::integral_constant<int, 64>{});
   }
+}
+
+// ---- one unit of a row: full = one 16-B access, straddling = guarded
+// scalar accesses, past D = zeros / nothing ---------------------------------
+__device__ __forceinline__ void load_unit(float (&v)[4], const float* p,
+                                          int nvalid) {
+  if (nvalid == 4) {
+    load_f32x4(p, v);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = j < nvalid ? p[j] : 0.f;
+  }
+}
+__device__ __forceinline__ void load_unit(float (&v)[8], const float* p,
+                                          int nvalid) {
+  if (nvalid == 8) {
+    load_f32x4(p, v);
+    load_f32x4(p + 4, v + 4);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = j < nvalid ? p[j] : 0.f;
+  }
+}
+// bf16 rows are whole units (D % 8 == 0)
+__device__ __forceinline__ void load_unit(float (&v)[8],
+                                          const unsigned short* p,
+                                          int nvalid) {
+  if (nvalid == 8) {
+    load_bf16x8(p, v);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+  }
+}
+__device__ __forceinline__ void store_unit(float* p, const float (&v)[4],
+                                           int nvalid) {
+  if (nvalid == 4) {
+    store_vec(p, v);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nvalid) p[j] = v[j];
+  }
+}
+__device__ __forceinline__ void store_unit(unsigned short* p,
+                                           const float (&v)[8], int nvalid) {
+  if (nvalid == 8) store_vec(p, v);
 }

@@ -59,7 +59,7 @@ class GCN(torch.nn.Module):
                     glorot_uniform((dims[i], dims[i + 1]), seed=seed + 1000 + i)))
             else:
                 self.res_proj.append(torch.nn.Parameter(torch.empty(0)))
-        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims, self)
 
     norm_parameters = norm_parameters
 
@@ -102,7 +102,7 @@ class GCN(torch.nn.Module):
                                  **drop),
                 shard)
         if i < len(self.weights) - 1:
-            h = hidden_act(self, i, h)
+            h = hidden_act(self, i, h, shard, group)
         if self.residual:
             proj = self.res_proj[i]
             if proj.numel() > 0:

@@ -36,7 +36,7 @@ class GIN(torch.nn.Module):
                 glorot_uniform((dims[i], hid), seed=seed + 2 * i)))
             self.w2.append(torch.nn.Parameter(
                 glorot_uniform((hid, dims[i + 1]), seed=seed + 2 * i + 1)))
-        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims, self)
 
     norm_parameters = norm_parameters
 
@@ -50,7 +50,7 @@ class GIN(torch.nn.Module):
         h = F.linear(h, self.w1[i], activation="relu")
         h = F.linear(h, self.w2[i])
         if i < len(self.w1) - 1:
-            h = hidden_act(self, i, h)
+            h = hidden_act(self, i, h, shard, group)
         return h
 
     def forward(self, x, shard, group=None):

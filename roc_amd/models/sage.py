@@ -58,7 +58,7 @@ class GraphSAGE(torch.nn.Module):
                 glorot_uniform((dims[i], dims[i + 1]), seed=seed + 2 * i)))
             self.w_neigh.append(torch.nn.Parameter(
                 glorot_uniform((dims[i], dims[i + 1]), seed=seed + 2 * i + 1)))
-        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims)
+        self.norm_gamma, self.norm_beta = make_norm_params(norm, dims, self)
 
     norm_parameters = norm_parameters
 
@@ -97,7 +97,7 @@ class GraphSAGE(torch.nn.Module):
                            group=group, **drop)  # fused mean
         h = F.add(h_self, hn)
         if i < len(self.w_self) - 1:
-            h = hidden_act(self, i, h)
+            h = hidden_act(self, i, h, shard, group)
         return h
 
     def forward_blocks(self, x, blocks):

@@ -1203,6 +1203,161 @@ def layer_norm(x, gamma, beta, eps: float = 1e-5,
 
 
 # ---------------------------------------------------------------------------
+# BatchNorm (+ fused ReLU), over the nodes of all shards
+# ---------------------------------------------------------------------------
+
+def _in_backward_pass() -> bool:
+    """True inside a checkpoint's re-forward (it runs in the backward pass);
+    the running statistics were already advanced by the first forward."""
+    return torch._C._current_graph_task_id() != -1
+
+
+class _BatchNorm(torch.autograd.Function):
+    """y = act(((x - mean_j) * rstd_j) * gamma_j + beta_j) with column
+    statistics over the rows of every rank (batch_norm.hip). Saves x and the
+    fp32 [D] mean and rstd; the backward recomputes x-hat and the relu mask,
+    so no [N, D] intermediate is kept. The cross-rank merges are all_reduce
+    only (capturable). dgamma / dbeta returned to autograd are this rank's
+    sums: the trainer's gradient all-reduce adds them over ranks."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training,
+                momentum, eps, relu, group, world_size, n, update):
+        x = x.contiguous()
+        hip = _hip(x)
+        if training:
+            if hip:
+                mean = torch.empty(x.shape[1], dtype=torch.float32,
+                                   device=x.device)
+                m2 = torch.empty_like(mean)
+                _C.batch_norm_stats(mean, m2, x)
+            else:
+                mean, m2 = ref.batch_norm_stats(x)
+            if world_size > 1:
+                import torch.distributed as dist
+                n_r = x.shape[0]
+                mean_g = mean * n_r
+                dist.all_reduce(mean_g, group=group)
+                mean_g /= n
+                m2 = m2 + n_r * (mean - mean_g) ** 2
+                dist.all_reduce(m2, group=group)
+                mean = mean_g
+            rm, rv = (running_mean, running_var) if update else (None, None)
+            if hip:
+                rstd = torch.empty_like(mean)
+                _C.batch_norm_finalize(rstd, mean, m2, rm, rv, n, momentum,
+                                       eps)
+            else:
+                rstd = ref.batch_norm_finalize(mean, m2, n, eps, rm, rv,
+                                               momentum)
+        else:
+            mean = running_mean.to(gamma.dtype)
+            rstd = 1.0 / torch.sqrt(running_var.to(gamma.dtype) + eps)
+        if hip:
+            y = torch.empty_like(x)
+            _C.batch_norm_apply(y, x, mean, rstd, gamma, beta, relu)
+        else:
+            y = ref.batch_norm_apply(x, mean, rstd, gamma, beta, relu)
+        ctx.save_for_backward(x, mean, rstd, gamma, beta)
+        ctx.cfg = (training, relu, group, world_size, n)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, gamma, beta = ctx.saved_tensors
+        training, relu, group, world_size, n = ctx.cfg
+        dy = dy.contiguous()
+        hip = _hip(dy)
+        if hip:
+            sums = torch.empty(2, x.shape[1], dtype=torch.float32,
+                               device=x.device)
+            _C.batch_norm_bwd_reduce(sums[0], sums[1], dy, x, mean, rstd,
+                                     gamma, beta, relu)
+        else:
+            sums = torch.stack(ref.batch_norm_bwd_reduce(
+                dy, x, mean, rstd, gamma, beta, relu))
+        dgamma, dbeta = sums[0].to(gamma.dtype), sums[1].to(beta.dtype)
+        if not training:
+            # fixed statistics: dx = gamma * rstd * g, the formula at S = 0
+            tot, n = torch.zeros_like(sums), max(x.shape[0], 1)
+        elif world_size > 1:
+            import torch.distributed as dist
+            tot = sums.clone()  # the returned gradients stay local
+            dist.all_reduce(tot, group=group)
+        else:
+            tot = sums
+        if hip:
+            dx = torch.empty_like(x)
+            _C.batch_norm_bwd_dx(dx, dy, x, mean, rstd, gamma, beta, tot[1],
+                                 tot[0], n, relu)
+        else:
+            dx = ref.batch_norm_bwd_dx(dy, x, mean, rstd, gamma, beta,
+                                       tot[1], tot[0], n, relu)
+        return (dx, dgamma, dbeta) + (None,) * 10
+
+
+def batch_norm(x, gamma, beta, running_mean=None, running_var=None,
+               training: bool = True, momentum: float = 0.1,
+               eps: float = 1e-5, activation: Optional[str] = None,
+               group=None, world_size: int = 1,
+               n_total: Optional[int] = None):
+    """BatchNorm over the rows (nodes) of [N, D] with an optional fused ReLU.
+
+    x: this rank's rows; bf16 (D % 8 == 0) or fp32 on GPU, any D. gamma,
+    beta: fp32 [D] masters (fp64 next to an fp64 x on CPU, for gradcheck).
+    running_mean / running_var: fp32 [D] buffers or None. In training the
+    statistics are those of the batch: at world_size > 1 of the n_total rows
+    of all ranks, merged with all_reduce over `group`, and every rank must
+    call (a rank with no rows too). The running buffers advance in place,
+    once per step: a checkpoint's re-forward inside the backward pass leaves
+    them alone. In eval the running buffers normalise. Every argument is
+    checked here, before any launch."""
+    if activation not in (None, "relu"):
+        raise ValueError(
+            f"activation must be None or 'relu', got {activation!r}")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"x must be [N, D >= 1], got {tuple(x.shape)}")
+    D = x.shape[1]
+    if x.is_cuda and x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"batch_norm on GPU takes bf16 or fp32, got {x.dtype}")
+    if x.dtype == torch.bfloat16 and D % 8 != 0:
+        raise ValueError(
+            f"bf16 rows must be a multiple of 8 wide (16 B), got D = {D}")
+    ok = (torch.float32, torch.float64) if x.dtype == torch.float64 \
+        else (torch.float32,)
+    for name, p in (("gamma", gamma), ("beta", beta)):
+        if p.dtype not in ok or tuple(p.shape) != (D,):
+            raise ValueError(
+                f"{name} must be fp32 [{D}], got {p.dtype} {tuple(p.shape)}")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("pass both running buffers, or neither")
+    for name, p in (("running_mean", running_mean),
+                    ("running_var", running_var)):
+        if p is not None and (p.dtype != torch.float32
+                              or tuple(p.shape) != (D,)
+                              or not p.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp32 [{D}] "
+                             f"buffer, got {p.dtype} {tuple(p.shape)}")
+    if not training and running_mean is None:
+        raise ValueError("eval mode normalises with the running buffers")
+    if world_size > 1 and n_total is None:
+        raise ValueError("world_size > 1 needs n_total, the global row count")
+    n = x.shape[0] if n_total is None or world_size == 1 else int(n_total)
+    if not 0 < momentum <= 1 or eps <= 0:
+        raise ValueError(f"need 0 < momentum <= 1 and eps > 0, got "
+                         f"{momentum}, {eps}")
+    if training and n < 1:
+        raise ValueError("training-mode batch_norm needs at least one row")
+    update = training and running_mean is not None \
+        and not _in_backward_pass()
+    return _BatchNorm.apply(x, gamma.contiguous(), beta.contiguous(),
+                            running_mean, running_var, bool(training),
+                            float(momentum), float(eps),
+                            activation == "relu", group, int(world_size), n,
+                            update)
+
+
+# ---------------------------------------------------------------------------
 # Linear (hand-written MFMA GEMM on GPU)
 # ---------------------------------------------------------------------------
 

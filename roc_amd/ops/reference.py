@@ -344,6 +344,109 @@ def layer_norm_grad(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
     return dx.to(x.dtype), (g * xh).sum(dim=0), g.sum(dim=0)
 
 
+def batch_norm_stats(x: torch.Tensor):
+    """Column statistics of [N, D] in the kernel's meaning
+    (`csrc/batch_norm.hip`): (mean [D], m2 [D]) with m2 the sum of squared
+    deviations, the centred second pass. Zero rows give zeros."""
+    ct = _ln_compute_dtype(x)
+    xf = x.to(ct)
+    if x.shape[0] == 0:
+        z = torch.zeros(x.shape[1], dtype=ct, device=x.device)
+        return z, z.clone()
+    mean = xf.sum(dim=0) / x.shape[0]
+    d = xf - mean
+    return mean, (d * d).sum(dim=0)
+
+
+def batch_norm_finalize(mean: torch.Tensor, m2: torch.Tensor, n: int,
+                        eps: float, running_mean=None, running_var=None,
+                        momentum: float = 0.1) -> torch.Tensor:
+    """rstd = 1/sqrt(m2/n + eps) from the (global) mean, m2 and row count.
+    Given the running buffers, advances them in place by one step:
+    running_var takes the unbiased m2/(n-1) (torch.nn.BatchNorm1d's
+    convention) and is left alone at n = 1."""
+    rstd = 1.0 / torch.sqrt(m2 / n + eps)
+    if running_mean is not None:
+        running_mean.mul_(1.0 - momentum).add_(
+            momentum * mean.to(running_mean.dtype))
+        if n > 1:
+            running_var.mul_(1.0 - momentum).add_(
+                momentum * (m2 / (n - 1)).to(running_var.dtype))
+    return rstd
+
+
+def batch_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor,
+                     gamma: torch.Tensor, beta: torch.Tensor,
+                     relu: bool = False) -> torch.Tensor:
+    """y = act(((x - mean_j) * rstd_j) * gamma_j + beta_j), in x's dtype."""
+    ct = _ln_compute_dtype(x)
+    y = ((x.to(ct) - mean.to(ct)) * rstd.to(ct)) * gamma.to(ct) + beta.to(ct)
+    if relu:
+        y = torch.relu(y)
+    return y.to(x.dtype)
+
+
+def batch_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+               running_mean=None, running_var=None, training: bool = True,
+               momentum: float = 0.1, eps: float = 1e-5, relu: bool = False):
+    """BatchNorm (+ ReLU) over the rows of one rank's [N, D] in the kernels'
+    formulas. Training normalises with the batch statistics and advances the
+    running buffers in place; eval normalises with the running buffers.
+    Returns (y, mean [D], rstd [D]); the reference has no normalization
+    layer."""
+    if training:
+        mean, m2 = batch_norm_stats(x)
+        rstd = batch_norm_finalize(mean, m2, x.shape[0], eps, running_mean,
+                                   running_var, momentum)
+    else:
+        mean, rstd = running_mean, 1.0 / torch.sqrt(running_var + eps)
+    return batch_norm_apply(x, mean, rstd, gamma, beta, relu), mean, rstd
+
+
+def batch_norm_bwd_reduce(dy: torch.Tensor, x: torch.Tensor,
+                          mean: torch.Tensor, rstd: torch.Tensor,
+                          gamma: torch.Tensor, beta: torch.Tensor,
+                          relu: bool = False):
+    """(dgamma, dbeta) = (sum_rows g*xh, sum_rows g) over this rank's rows;
+    xh is recomputed, the relu mask is xh*gamma+beta > 0."""
+    ct = _ln_compute_dtype(x)
+    xh = (x.to(ct) - mean.to(ct)) * rstd.to(ct)
+    g = dy.to(ct)
+    if relu:
+        g = torch.where(xh * gamma.to(ct) + beta.to(ct) > 0, g,
+                        torch.zeros_like(g))
+    return (g * xh).sum(dim=0), g.sum(dim=0)
+
+
+def batch_norm_bwd_dx(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
+                      rstd: torch.Tensor, gamma: torch.Tensor,
+                      beta: torch.Tensor, s_g: torch.Tensor,
+                      s_gx: torch.Tensor, n: int, relu: bool = False):
+    """dx = (gamma*rstd) * ((g - S_g/n) - xh * S_gx/n) from the GLOBAL
+    column sums S_g = sum g, S_gx = sum g*xh and the global row count."""
+    ct = _ln_compute_dtype(x)
+    gam, r = gamma.to(ct), rstd.to(ct)
+    xh = (x.to(ct) - mean.to(ct)) * r
+    g = dy.to(ct)
+    if relu:
+        g = torch.where(xh * gam + beta.to(ct) > 0, g, torch.zeros_like(g))
+    dx = (gam * r) * ((g - s_g.to(ct) / n) - xh * (s_gx.to(ct) / n))
+    return dx.to(x.dtype)
+
+
+def batch_norm_grad(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor,
+                    rstd: torch.Tensor, gamma: torch.Tensor,
+                    beta: torch.Tensor, relu: bool = False):
+    """Training-mode gradient of batch_norm on one rank from the saved
+    column statistics. Returns (dx in x's dtype, dgamma, dbeta in the
+    compute dtype)."""
+    dgamma, dbeta = batch_norm_bwd_reduce(dy, x, mean, rstd, gamma, beta,
+                                          relu)
+    dx = batch_norm_bwd_dx(dy, x, mean, rstd, gamma, beta, dbeta, dgamma,
+                           x.shape[0], relu)
+    return dx, dgamma, dbeta
+
+
 def degnorm(x: torch.Tensor, deg: torch.Tensor) -> torch.Tensor:
     """out[v] = x[v] / sqrt(indeg(v))  (reference `graphnorm_kernel.cu:19-57`)."""
     return x * torch.rsqrt(deg.clamp(min=1.0)).unsqueeze(1).to(x.dtype)

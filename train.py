@@ -10,7 +10,7 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer,
+--model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer|batch,
 --edge-drop P, --dtype,
 --checkpoint/--resume, --trace.
 """
@@ -52,10 +52,12 @@ def parse_args():
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
-    ap.add_argument("--norm", default="none", choices=["none", "layer"],
+    ap.add_argument("--norm", default="none", choices=["none", "layer", "batch"],
                     help="hidden-layer normalization of --model gcn, sage, "
                          "gin, transformer or gatv2: layer = fused per-node "
-                         "LayerNorm + ReLU")
+                         "LayerNorm + ReLU; batch (gcn, sage, gin) = "
+                         "BatchNorm + ReLU over the nodes of all ranks, "
+                         "running statistics in eval")
     ap.add_argument("--epochs", "-e", type=int, default=100)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -176,8 +178,10 @@ def parse_args():
                  "(--aggr mean) or gin")
     if args.edge_drop and args.gather_dtype == "fp8":
         ap.error("--edge-drop does not combine with --gather-dtype fp8")
-    if args.norm not in ("none", "layer"):  # a YAML value
-        ap.error(f"--norm must be none or layer, got {args.norm!r}")
+    if args.norm not in ("none", "layer", "batch"):  # a YAML value
+        ap.error(f"--norm must be none, layer or batch, got {args.norm!r}")
+    if args.norm == "batch" and args.model not in ("gcn", "sage", "gin"):
+        ap.error("--norm batch needs --model gcn, sage or gin")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
                                                   "transformer", "gatv2",
                                                   "pna"):
@@ -290,7 +294,8 @@ def main():
         if args.k_hops:
             mkw["k"] = args.k_hops
     if args.norm != "none":
-        mkw["norm"] = args.norm
+        # the models spell it "sync_batch": the statistics span all ranks
+        mkw["norm"] = "sync_batch" if args.norm == "batch" else args.norm
     if args.edge_drop:
         mkw["edge_drop"] = float(args.edge_drop)
     model = build_model(args.model, dims, dropout=args.dropout,
