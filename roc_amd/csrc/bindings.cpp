@@ -72,6 +72,15 @@ void seg_stats_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor x,
                    torch::Tensor rowptr, torch::Tensor t_rowptr,
                    torch::Tensor t_colidx, torch::Tensor t_eperm,
                    c10::optional<torch::Tensor> t_row_order, int64_t depth);
+void seg_softmax_fwd(torch::Tensor out, c10::optional<torch::Tensor> stats,
+                     torch::Tensor x, torch::Tensor t, torch::Tensor rowptr,
+                     torch::Tensor colidx,
+                     c10::optional<torch::Tensor> row_order, int64_t depth);
+void seg_softmax_bwd(torch::Tensor dx, c10::optional<torch::Tensor> dt_out,
+                     torch::Tensor dy, torch::Tensor x, torch::Tensor stats,
+                     torch::Tensor t, torch::Tensor t_rowptr,
+                     torch::Tensor t_colidx,
+                     c10::optional<torch::Tensor> t_row_order, int64_t depth);
 void layer_norm_fwd(torch::Tensor y, c10::optional<torch::Tensor> mean,
                     c10::optional<torch::Tensor> rstd, torch::Tensor x,
                     torch::Tensor gamma, torch::Tensor beta, double eps,
@@ -260,6 +269,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("rowptr"), pybind11::arg("t_rowptr"),
         pybind11::arg("t_colidx"),
         pybind11::arg("t_eperm"),
+        pybind11::arg("t_row_order") = pybind11::none(),
+        pybind11::arg("depth") = 0);
+  m.def("seg_softmax_fwd", &seg_softmax_fwd,
+        "CSR per-column softmax aggregation in one gather: out = sum_e "
+        "softmax_e(t*x)*x, stats = fp32 [lse|out32]; stats = None skips its "
+        "stores; t is a fp32 [1] device tensor",
+        pybind11::arg("out"), pybind11::arg("stats"), pybind11::arg("x"),
+        pybind11::arg("t"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order") = pybind11::none(),
+        pybind11::arg("depth") = 0);
+  m.def("seg_softmax_bwd", &seg_softmax_bwd,
+        "seg_softmax gradient: one gather of stats and dy over the transpose "
+        "CSR; dt_out (fp32 [1], overwritten) = None skips the dt reduction",
+        pybind11::arg("dx"), pybind11::arg("dt_out"), pybind11::arg("dy"),
+        pybind11::arg("x"), pybind11::arg("stats"), pybind11::arg("t"),
+        pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
         pybind11::arg("t_row_order") = pybind11::none(),
         pybind11::arg("depth") = 0);
   m.def("layer_norm_fwd", &layer_norm_fwd,

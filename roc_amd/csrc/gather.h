@@ -1,6 +1,6 @@
 // 16-B row-gather helpers shared by the row-team CSR kernels that read
 // feature rows through colidx (spmm.hip, seg_max.hip, seg_stats.hip,
-// graph_attn.hip):
+// seg_softmax.hip, graph_attn.hip):
 // the raw payload and its widen, the two gather engines and their
 // factory, one rung of the unroll ladder and the ladder itself.
 #pragma once
@@ -62,6 +62,36 @@ __device__ __forceinline__ void store_arg(int* p, const int (&a)[EPU]) {
   for (int q = 0; q < EPU; q += 4)
     *reinterpret_cast<int4*>(p + q) =
         make_int4(a[q], a[q + 1], a[q + 2], a[q + 3]);
+}
+
+// A 4-column unit in either dtype (float4 / 4 x bf16 in a uint2), for the
+// source-major backward launches whose slots also hold fp32 state
+// (seg_stats.hip, seg_softmax.hip): 8 columns a lane would double the VGPRs
+// of every edge in flight.
+template <typename T>
+struct Raw4 { using type = float4; };
+template <>
+struct Raw4<unsigned short> { using type = uint2; };
+
+__device__ __forceinline__ float4 load4(const float* p) {
+  return *reinterpret_cast<const float4*>(p);
+}
+__device__ __forceinline__ uint2 load4(const unsigned short* p) {
+  return *reinterpret_cast<const uint2*>(p);
+}
+__device__ __forceinline__ void widen4(float* v, const float4& r) {
+  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+}
+__device__ __forceinline__ void widen4(float* v, const uint2& r) {
+  v[0] = bf16_lo(r.x); v[1] = bf16_hi(r.x);
+  v[2] = bf16_lo(r.y); v[3] = bf16_hi(r.y);
+}
+__device__ __forceinline__ void store4(float* p, const float* a) {
+  store_f32x4(p, a);
+}
+__device__ __forceinline__ void store4(unsigned short* p, const float* a) {
+  *reinterpret_cast<uint2*>(p) =
+      make_uint2(pack_bf16(a[0], a[1]), pack_bf16(a[2], a[3]));
 }
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;

@@ -244,32 +244,6 @@ __global__ __launch_bounds__(kBlock) void seg_stats_fwd_kernel(
 // backward: 4 columns per lane
 // ---------------------------------------------------------------------------
 
-template <typename T>
-struct Raw4 { using type = float4; };
-template <>
-struct Raw4<unsigned short> { using type = uint2; };
-
-__device__ __forceinline__ float4 load4(const float* p) {
-  return *reinterpret_cast<const float4*>(p);
-}
-__device__ __forceinline__ uint2 load4(const unsigned short* p) {
-  return *reinterpret_cast<const uint2*>(p);
-}
-__device__ __forceinline__ void widen4(float* v, const float4& r) {
-  v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-}
-__device__ __forceinline__ void widen4(float* v, const uint2& r) {
-  v[0] = bf16_lo(r.x); v[1] = bf16_hi(r.x);
-  v[2] = bf16_lo(r.y); v[3] = bf16_hi(r.y);
-}
-__device__ __forceinline__ void store4(float* p, const float* a) {
-  store_f32x4(p, a);
-}
-__device__ __forceinline__ void store4(unsigned short* p, const float* a) {
-  *reinterpret_cast<uint2*>(p) =
-      make_uint2(pack_bf16(a[0], a[1]), pack_bf16(a[2], a[3]));
-}
-
 // in-degree of destination row v from the low words of its rowptr pair
 // (check_csr_i32 keeps every edge offset below 2^31)
 __device__ __forceinline__ int2 load_deg(const int64_t* __restrict__ rowptr,

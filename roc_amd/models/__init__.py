@@ -7,6 +7,7 @@ from .gatv2 import GATv2
 from .sgc import SGC
 from .appnp import APPNP
 from .pna import PNA, pna_delta
+from .deepergcn import DeeperGCN
 
 
 def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
@@ -29,4 +30,6 @@ def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
         return APPNP(dims, dropout=dropout, seed=seed, **kw)
     if name == "pna":
         return PNA(dims, dropout=dropout, seed=seed, **kw)
+    if name == "deepergcn":
+        return DeeperGCN(dims, dropout=dropout, seed=seed, **kw)
     raise ValueError(f"unknown model {name!r}")

@@ -859,6 +859,99 @@ def scatter_gather_stats(x, shard, eps: float = 1e-5):
         shard.row_order, shard.t_row_order)
 
 
+class _SegSoftmax(torch.autograd.Function):
+    """out[v, j] = sum_e softmax_e(t * x[u_e, j]) * x[u_e, j] over the
+    in-neighbours of v, one softmax per column, out of one gather of each
+    neighbour row (seg_softmax.hip). When x or t needs a gradient the
+    forward also saves stats, fp32 [lse | out] with the log-sum-exp of the
+    scores centred on out (the backward never sees the rounded out). The backward is one deterministic gather over the
+    transpose CSR: no edge permutation, no atomics; dt is folded in a fixed
+    order and is skipped when t needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, t, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                num_src, row_order, t_row_order):
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        x = x.contiguous()
+        if _hip(x):
+            out = torch.empty(num_rows, x.shape[1], dtype=x.dtype,
+                              device=x.device)
+            stats = None
+            if need_grad:
+                stats = torch.empty(num_rows, 2 * x.shape[1],
+                                    dtype=torch.float32, device=x.device)
+            _C.seg_softmax_fwd(out, stats, x, t, rowptr, colidx, row_order)
+        else:
+            out, stats = ref.seg_softmax(x, t, rowptr, colidx, num_rows)
+        ctx.num_src = num_src
+        if need_grad:
+            if x.is_cuda:
+                ctx.save_for_backward(x, stats, t, t_rowptr, t_colidx,
+                                      t_row_order)
+            else:
+                ctx.save_for_backward(x, stats, t, rowptr, colidx)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        dt = None
+        if _hip(dy):
+            x, stats, t, t_rowptr, t_colidx, t_row_order = ctx.saved_tensors
+            dx = torch.empty_like(x)
+            if ctx.needs_input_grad[1]:
+                dt = torch.empty_like(t)
+            _C.seg_softmax_bwd(dx, dt, dy, x, stats, t, t_rowptr, t_colidx,
+                               t_row_order)
+        else:
+            x, stats, t, rowptr, colidx = ctx.saved_tensors
+            dx, dt = ref.seg_softmax_grad(dy, x, stats, t, rowptr, colidx,
+                                          ctx.num_src)
+            dt = dt.to(t.dtype).view_as(t)
+        return (dx, dt) + (None,) * 8
+
+
+def seg_softmax_csr(x, t, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                    num_src, row_order=None, t_row_order=None):
+    """scatter_gather_softmax over an explicit CSR / transpose-CSR pair.
+    Every argument is checked here, before any launch."""
+    if x.dim() != 2 or x.shape[0] != num_src:
+        # colidx indexes x unchecked on the GPU: a short x reads out of bounds
+        raise ValueError(f"x must be [{num_src}, D], got {tuple(x.shape)}")
+    if x.is_cuda and x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(
+            f"scatter_gather_softmax on GPU takes bf16 or fp32, got {x.dtype}")
+    ok = (torch.float32, torch.float64) if x.dtype == torch.float64 \
+        else (torch.float32,)
+    if not torch.is_tensor(t) or t.dtype not in ok or t.numel() != 1:
+        raise ValueError("the temperature must be a fp32 tensor of one "
+                         "element (read on the device, never on the host)")
+    if t.device != x.device:
+        raise ValueError("x and the temperature must live on one device")
+    return _SegSoftmax.apply(x, t, rowptr, colidx, t_rowptr, t_colidx,
+                             num_rows, num_src, row_order, t_row_order)
+
+
+def scatter_gather_softmax(x, shard, t):
+    """DeeperGCN's softmax aggregation over the shard's local CSR (Li et al.
+    2020, PyG's GENConv with aggr="softmax").
+
+    x: [n_ext, D] halo-extended features; t: the temperature, a fp32 tensor
+    of one element on x's device (a learnable parameter or a buffer). For
+    row v, column j and in-edge e from u_e:
+      p_e = softmax_e(t * x[u_e, j]),   out[v, j] = sum_e p_e * x[u_e, j]
+    t = 0 is the mean and t -> inf the max. Returns [n_local, D] in x's
+    dtype (bf16 or fp32 on GPU; all arithmetic is fp32, one rounding at the
+    store). Duplicate edges each count; a row without edges gives 0 and
+    passes no gradient; a source without out-edges gets a zero gradient.
+    The gradient of t is reduced without atomics in a fixed order:
+    bit-reproducible from run to run. `shard` may be a GraphShard or a
+    sampling Block."""
+    return seg_softmax_csr(
+        x, t, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+        shard.n_local, shard.n_ext, shard.row_order, shard.t_row_order)
+
+
 # ---------------------------------------------------------------------------
 # Dot-product graph attention (fused online-softmax kernels)
 # ---------------------------------------------------------------------------

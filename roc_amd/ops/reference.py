@@ -226,6 +226,71 @@ def seg_stats_grad(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor,
     return dx.to(dy.dtype)
 
 
+def seg_softmax(x: torch.Tensor, t: torch.Tensor, rowptr: torch.Tensor,
+                colidx: torch.Tensor, num_rows: int):
+    """DeeperGCN's softmax aggregation (Li et al. 2020; PyG's GENConv): per
+    row v and column j, over the edges e of the row,
+      p_e = softmax_e(t * x[u_e, j]),   out[v, j] = sum_e p_e * x[u_e, j]
+    with one temperature t (a tensor of one element) for all columns.
+    Returns (out, stats): out [num_rows, D] in x's dtype and stats
+    [num_rows, 2*D] = [lse | out], unrounded (fp32; fp64 stays), where
+    lse = log sum_e exp(t * (x[u_e, j] - out[v, j])), the log-sum-exp of the
+    scores centred on the output: it stays of the size of log(deg) where the
+    plain one is as large as t * x. The weighted sum is shifted by the
+    row's first edge, as seg_stats shifts its sums. Duplicate edges each
+    count; an empty row gives 0 everywhere. NaN and +-inf are out of
+    contract. The reference has no such aggregator."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    D = x.shape[1]
+    E = int(colidx.numel())
+    zeros = torch.zeros(num_rows, D, dtype=ct, device=x.device)
+    if E == 0:
+        return zeros.to(x.dtype), torch.cat([zeros, zeros], 1)
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=x.device), deg)
+    empty = (deg == 0).unsqueeze(1)
+    src = colidx.to(torch.long)
+    xs = x.to(ct)[src]                                     # [E, D]
+    s = t.to(ct).reshape(()) * xs
+    m = zeros.scatter_reduce(0, dst.unsqueeze(1).expand(E, D), s,
+                             reduce="amax", include_self=False)
+    p = torch.exp(s - m[dst])
+    l = zeros.index_add(0, dst, p)
+    # a trailing empty row starts at E: clamped, then masked
+    x0 = xs[rowptr[:-1].to(torch.long).clamp(max=E - 1)].masked_fill(empty, 0)
+    a = zeros.index_add(0, dst, p * (xs - x0[dst]))
+    out = (x0 + a / l.clamp(min=1)).masked_fill(empty, 0)
+    tc = t.to(ct).reshape(())
+    lse = ((m - tc * out) + torch.log(l.clamp(min=1))).masked_fill(empty, 0)
+    return out.to(x.dtype), torch.cat([lse, out], 1)
+
+
+def seg_softmax_grad(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor,
+                     t: torch.Tensor, rowptr: torch.Tensor,
+                     colidx: torch.Tensor, num_src: int):
+    """(dx, dt) of seg_softmax from dy [num_rows, D] and the saved stats.
+    Every edge (u, v) carries, with d = x[u] - out[v] and
+    p = exp(t*d - lse[v]):  dx[u] += p * dy[v] * (1 + t*d),  dt += p * dy[v] * d^2
+    (the squared form of sum p*dy*x*d: sum_e p*d = 0, and its terms do not
+    cancel). dt is a tensor of one element in stats' dtype."""
+    ct = stats.dtype
+    D = x.shape[1]
+    num_rows = dy.shape[0]
+    lse, out = stats.split(D, 1)
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=x.device), deg)
+    src = colidx.to(torch.long)
+    tc = t.to(ct).reshape(())
+    xs = x.to(ct)[src]
+    d = xs - out[dst]
+    w = torch.exp(tc * d - lse[dst]) * dy.to(ct)[dst]
+    dx = torch.zeros(num_src, D, dtype=ct, device=x.device)
+    dx.index_add_(0, src, w * (1.0 + tc * d))
+    return dx.to(dy.dtype), (w * d * d).sum().reshape(1)
+
+
 def graph_attention(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
                     colidx: torch.Tensor, num_rows: int, heads: int,
                     scale: float) -> torch.Tensor:

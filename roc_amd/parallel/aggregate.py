@@ -185,13 +185,31 @@ class _GatherBlocks(torch.autograd.Function):
         return dx_pad[:shard.n_local].contiguous(), None, None
 
 
-def _aggregate_reduce(x, shard, reduce, group):
-    """max / min / stats neighbor aggregation of the local block. The
-    exchange completes before the local op starts: there is no
-    comm/compute-overlap variant here (merging partial extrema, their args
-    and the shifted sums across the self/remote edge split is a
-    follow-up), whatever ROC_OVERLAP / ROC_AG_OVERLAP say."""
+def _aggregate_reduce(x, shard, reduce, group, temperature=None):
+    """max / min / stats / softmax neighbor aggregation of the local block.
+    The exchange completes before the local op starts: there is no
+    comm/compute-overlap variant here (merging partial extrema, their args,
+    the shifted sums and the softmax states across the self/remote edge
+    split is a follow-up), whatever ROC_OVERLAP / ROC_AG_OVERLAP say."""
     from ..ops import functional as Fn
+    if reduce == "softmax":
+        if temperature is None:
+            raise ValueError("reduce='softmax' needs temperature=t, a fp32 "
+                             "tensor of one element")
+        if shard.world_size == 1:
+            return Fn.scatter_gather_softmax(x, shard, temperature)
+        if shard.comm_mode == "allgather":
+            # no edge permutation here: the backward gathers by t_colidx
+            gathered = _GatherBlocks.apply(x, shard, group)
+            cuda = x.is_cuda
+            return Fn.seg_softmax_csr(
+                gathered, temperature, shard.rowptr, shard.ag_colidx,
+                shard.ag_t_rowptr, shard.ag_t_colidx, shard.n_local,
+                shard.world_size * shard.ag_max_rows,
+                row_order=shard.row_order if cuda else None,
+                t_row_order=shard.ag_t_row_order if cuda else None)
+        return Fn.scatter_gather_softmax(halo_exchange(x, shard, group),
+                                         shard, temperature)
     if reduce == "stats":
         def local(xe):
             return Fn.scatter_gather_stats(xe, shard)
@@ -241,15 +259,20 @@ def _aggregate_drop(x, shard, dst_scale, group, p, call_id):
 
 def aggregate(x, shard, dst_scale=None, group=None, reduce="sum",
               edge_drop: float = 0.0, training: bool = False,
-              edge_call_id=None):
+              edge_call_id=None, temperature=None):
     """Distributed neighbor aggregation of the LOCAL feature block.
     Returns [n_local, D]. reduce="sum" (+ optional fused dst-side degree
     scale) is the sum / mean path; reduce="max" | "min" takes the
     elementwise extremum over in-neighbors (first edge wins ties, empty
     rows give 0; see ops.functional.scatter_gather_reduce);
     reduce="stats" returns [n_local, 4*D], the PNA aggregators
-    [mean | std | max | min] (ops.functional.scatter_gather_stats).
-    Neither takes a dst_scale. They exchange first and aggregate after, in
+    [mean | std | max | min] (ops.functional.scatter_gather_stats);
+    reduce="softmax" with temperature=t (a fp32 tensor of one element on
+    x's device) is DeeperGCN's per-column softmax aggregation
+    (ops.functional.scatter_gather_softmax); each rank's gradient of t
+    covers its local edges, and the trainer's gradient all-reduce sums it
+    like that of any replicated parameter.
+    None of them takes a dst_scale. They exchange first and aggregate after, in
     every comm mode: they have no comm/compute-overlap variant yet.
     edge_drop=p with training=True (reduce="sum" only) is DropEdge, see
     ops.functional.scatter_gather; it too exchanges first and aggregates
@@ -264,7 +287,7 @@ def aggregate(x, shard, dst_scale=None, group=None, reduce="sum",
     if reduce != "sum":
         if dst_scale is not None:
             raise ValueError("dst_scale applies to reduce='sum' only")
-        return _aggregate_reduce(x, shard, reduce, group)
+        return _aggregate_reduce(x, shard, reduce, group, temperature)
     if shard.world_size == 1:
         return Fn.scatter_gather(x, shard, dst_scale=dst_scale)
     if shard.comm_mode == "allgather":

@@ -10,7 +10,7 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|gatv2|transformer|pna, --norm none|layer|batch,
+--model gcn|sage|gin|gat|gatv2|transformer|pna|deepergcn, --norm none|layer|batch,
 --edge-drop P, --dtype,
 --checkpoint/--resume, --trace.
 """
@@ -47,15 +47,16 @@ def parse_args():
                          "e.g. 602-256-41")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
-    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "gatv2", "transformer", "pna", "sgc",
+    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "gatv2", "transformer", "pna", "deepergcn", "sgc",
                              "appnp"])
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
     ap.add_argument("--norm", default="none", choices=["none", "layer", "batch"],
                     help="hidden-layer normalization of --model gcn, sage, "
-                         "gin, transformer or gatv2: layer = fused per-node "
-                         "LayerNorm + ReLU; batch (gcn, sage, gin) = "
+                         "gin, transformer, gatv2, pna or deepergcn: layer = "
+                         "fused per-node LayerNorm + ReLU; batch (gcn, sage, "
+                         "gin, deepergcn) = "
                          "BatchNorm + ReLU over the nodes of all ranks, "
                          "running statistics in eval")
     ap.add_argument("--epochs", "-e", type=int, default=100)
@@ -180,14 +181,15 @@ def parse_args():
         ap.error("--edge-drop does not combine with --gather-dtype fp8")
     if args.norm not in ("none", "layer", "batch"):  # a YAML value
         ap.error(f"--norm must be none, layer or batch, got {args.norm!r}")
-    if args.norm == "batch" and args.model not in ("gcn", "sage", "gin"):
-        ap.error("--norm batch needs --model gcn, sage or gin")
+    if args.norm == "batch" and args.model not in ("gcn", "sage", "gin",
+                                                   "deepergcn"):
+        ap.error("--norm batch needs --model gcn, sage, gin or deepergcn")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
                                                   "transformer", "gatv2",
-                                                  "pna"):
+                                                  "pna", "deepergcn"):
         ap.error(f"--norm {args.norm} needs --model gcn, sage, gin, "
-                 f"transformer, gatv2 or pna: --model {args.model} has no "
-                 f"hidden-layer norm")
+                 f"transformer, gatv2, pna or deepergcn: --model "
+                 f"{args.model} has no hidden-layer norm")
     return args
 
 
@@ -309,7 +311,8 @@ def main():
                         decay_rate=args.decay_rate,
                         decay_steps=args.decay_steps,
                         no_decay=model.norm_parameters()
-                        if args.norm != "none" else ())
+                        if args.norm != "none" or args.model == "deepergcn"
+                        else ())
     dtype = torch.float32
     if args.dtype == "bf16" or (args.dtype == "auto" and on_gpu):
         dtype = torch.bfloat16
