@@ -8,7 +8,8 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           int64_t col_base, int64_t ncols,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
           c10::optional<torch::Tensor> final_out,
-          c10::optional<torch::Tensor> out_rows);
+          c10::optional<torch::Tensor> out_rows, bool relu,
+          c10::optional<torch::Tensor> post_scale);
 void quantize_rows_fp8(torch::Tensor q, torch::Tensor s, torch::Tensor x,
                        c10::optional<torch::Tensor> pre_scale);
 void spmm_fp8(torch::Tensor out, torch::Tensor q, torch::Tensor scale,
@@ -32,7 +33,8 @@ void cast_rowscale(torch::Tensor out, torch::Tensor x,
                    c10::optional<torch::Tensor> scale);
 void relu_fwd(torch::Tensor out, torch::Tensor x);
 void sigmoid_fwd(torch::Tensor out, torch::Tensor x);
-void relu_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y);
+void relu_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y,
+              c10::optional<torch::Tensor> row_scale);
 void sigmoid_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y);
 void ewise_add(torch::Tensor out, torch::Tensor a, torch::Tensor b);
 void ewise_mul(torch::Tensor out, torch::Tensor a, torch::Tensor b);
@@ -170,7 +172,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("heavy_rows") = pybind11::none(),
         pybind11::arg("heavy_min") = 0,
         pybind11::arg("final_out") = pybind11::none(),
-        pybind11::arg("out_rows") = pybind11::none());
+        pybind11::arg("out_rows") = pybind11::none(),
+        pybind11::arg("relu") = false,
+        pybind11::arg("post_scale") = pybind11::none());
   m.def("quantize_rows_fp8", &quantize_rows_fp8,
         "bf16 rows (times an optional fp32 row factor) -> e4m3 bytes and a "
         "power-of-two fp32 scale per row",
@@ -210,7 +214,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("scale") = pybind11::none());
   m.def("relu_fwd", &relu_fwd);
   m.def("sigmoid_fwd", &sigmoid_fwd);
-  m.def("relu_bwd", &relu_bwd);
+  m.def("relu_bwd", &relu_bwd,
+        "dx = (y > 0 ? dy : 0) (* row_scale[row], rounded as a rowscale pass "
+        "over the stored dx would)",
+        pybind11::arg("dx"), pybind11::arg("dy"), pybind11::arg("y"),
+        pybind11::arg("row_scale") = pybind11::none());
   m.def("sigmoid_bwd", &sigmoid_bwd);
   m.def("ewise_add", &ewise_add);
   m.def("ewise_mul", &ewise_mul);

@@ -117,6 +117,21 @@ __device__ __forceinline__ void f32_to_elt(float f, unsigned short* d) {
   *d = (unsigned short)f32_to_bf16(f);
 }
 
+// A row scaling folded into the store of the kernel that produced the
+// value must round as the two kernels it replaces did: the producer
+// rounded to its storage type ST, a rowscale pass widened that, multiplied
+// by the fp32 factor and rounded again at its own store. So: round to ST,
+// widen, multiply; the caller's store does the second rounding. One fp32
+// multiply and one rounding is NOT the same bf16 value.
+__device__ __forceinline__ float round_as(float v, float) { return v; }
+__device__ __forceinline__ float round_as(float v, unsigned short) {
+  return __uint_as_float(f32_to_bf16(v) << 16);
+}
+template <typename ST>
+__device__ __forceinline__ float scale_stored(float v, float s) {
+  return round_as(v, ST{}) * s;
+}
+
 constexpr int kBlock = 256;  // 4 wavefronts
 
 inline int roc_grid_1d(long long work, int per_block, int cap = 4096) {

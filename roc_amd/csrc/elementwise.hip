@@ -46,22 +46,32 @@ __global__ __launch_bounds__(kBlock) void map2_kernel(
       if constexpr (EPU == 8) { load_bf16x8(a + i0, va); load_bf16x8(b + i0, vb); }
       else                    { load_f32x4(a + i0, va);  load_f32x4(b + i0, vb); }
 #pragma unroll
-      for (int j = 0; j < EPU; ++j) va[j] = op(va[j], vb[j]);
+      for (int j = 0; j < EPU; ++j) va[j] = op(va[j], vb[j], i0 + j);
       if constexpr (EPU == 8) store_bf16x8(out + i0, va);
       else store_f32x4(out + i0, va);
     } else {
       for (int64_t i = i0; i < n; ++i)
-        f32_to_elt(op(elt_to_f32(a[i]), elt_to_f32(b[i])), out + i);
+        f32_to_elt(op(elt_to_f32(a[i]), elt_to_f32(b[i]), i), out + i);
     }
   }
 }
 
 struct OpRelu { __device__ float operator()(float x, int64_t) const { return x > 0.f ? x : 0.f; } };
 struct OpSigmoid { __device__ float operator()(float x, int64_t) const { return 1.f / (1.f + __expf(-x)); } };
-struct OpAdd { __device__ float operator()(float a, float b) const { return a + b; } };
-struct OpMul { __device__ float operator()(float a, float b) const { return a * b; } };
-struct OpReluBwd { __device__ float operator()(float dy, float y) const { return y > 0.f ? dy : 0.f; } };
-struct OpSigmoidBwd { __device__ float operator()(float dy, float y) const { return dy * y * (1.f - y); } };
+struct OpAdd { __device__ float operator()(float a, float b, int64_t) const { return a + b; } };
+struct OpMul { __device__ float operator()(float a, float b, int64_t) const { return a * b; } };
+struct OpReluBwd { __device__ float operator()(float dy, float y, int64_t) const { return y > 0.f ? dy : 0.f; } };
+struct OpSigmoidBwd { __device__ float operator()(float dy, float y, int64_t) const { return dy * y * (1.f - y); } };
+// relu_bwd then rowscale in one store. The masked value is dy itself or
+// 0, exact in the storage type, so the rounding scale_stored (common.h)
+// would do first is the identity here: one multiply, one rounding.
+struct OpReluBwdScale {
+  const float* scale;
+  int64_t D;
+  __device__ float operator()(float dy, float y, int64_t i) const {
+    return (y > 0.f ? dy : 0.f) * scale[i / D];
+  }
+};
 
 struct OpRowScale {
   const float* scale;
@@ -142,8 +152,19 @@ void relu_fwd(torch::Tensor out, torch::Tensor x) {
 void sigmoid_fwd(torch::Tensor out, torch::Tensor x) {
   dispatch_map1(out, x, OpSigmoid{});
 }
-void relu_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y) {
-  dispatch_map2(dx, dy, y, OpReluBwd{});
+void relu_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y,
+              c10::optional<torch::Tensor> row_scale) {
+  if (!row_scale.has_value()) {
+    dispatch_map2(dx, dy, y, OpReluBwd{});
+    return;
+  }
+  ROC_CHECK_DEV_CONT(*row_scale);
+  TORCH_CHECK(row_scale->scalar_type() == torch::kFloat32,
+              "relu_bwd: row_scale must be fp32");
+  TORCH_CHECK(dy.dim() == 2 && row_scale->numel() == dy.size(0),
+              "relu_bwd: row_scale needs one entry per row of dy");
+  dispatch_map2(dx, dy, y,
+                OpReluBwdScale{row_scale->data_ptr<float>(), dy.size(1)});
 }
 void sigmoid_bwd(torch::Tensor dx, torch::Tensor dy, torch::Tensor y) {
   dispatch_map2(dx, dy, y, OpSigmoidBwd{});

@@ -52,6 +52,13 @@ __device__ __forceinline__ void acc_add(float* acc, const float4& r, float w) {
 // live across all in-flight gathers).
 enum class Weight { kNone, kSrc, kEdge };  // 1 | w[u_e] | w[e]
 
+// What the store of a finished row does after the deg_dst scale (bf16
+// FINAL pass, or a plain pass with OT == T; no weight):
+//  kRelu  max(0, .) - exact, ReLU commutes with the rounding of the store
+//  kPost  times post_scale[dst], rounded as a separate rowscale pass over
+//         the stored row would have (scale_stored in common.h)
+enum class Epi { kNone, kRelu, kPost };
+
 // acc += w_e * x[u_e, unit] for N consecutive edges. Per-edge weights are
 // sequential, so they load before the gathers issue (one scalar broadcast
 // per gather); per-source weights are looked up as the payloads land.
@@ -147,7 +154,8 @@ __device__ void row_accum_tail(
 //         a buffer in plan order; only the pass that stores a finished row
 //         pays the index load. An entry outside [0, n_out) is skipped.
 template <typename T, typename OT, int TEAM, int UN, bool BUF, Weight W,
-          bool HEAVY = false, bool FINAL = false, bool PERM = false>
+          bool HEAVY = false, bool FINAL = false, bool PERM = false,
+          Epi EPI = Epi::kNone>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(
     OT* __restrict__ out, const T* __restrict__ x,
     const int64_t* __restrict__ rowptr, const int* __restrict__ colidx,
@@ -156,8 +164,11 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
     int64_t col_base, int64_t col_end, bool accumulate, unsigned x_bytes,
     const int* __restrict__ heavy_rows, int num_heavy, int heavy_min,
     unsigned short* __restrict__ final_out,
-    const int* __restrict__ out_rows, int n_out) {
+    const int* __restrict__ out_rows, int n_out,
+    const float* __restrict__ post_scale) {
   constexpr int EPU = EltTraits<T>::kPerVec;
+  // the type the finished row is stored as
+  using ST = std::conditional_t<FINAL, unsigned short, OT>;
   const RowTeam<TEAM> rt;
 
   const int64_t col0 =
@@ -184,6 +195,14 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
         const float s = deg_dst[dst];
 #pragma unroll
         for (int j = 0; j < EPU; ++j) acc[j] *= s;
+      }
+      if constexpr (EPI == Epi::kRelu) {
+#pragma unroll
+        for (int j = 0; j < EPU; ++j) acc[j] = acc[j] > 0.f ? acc[j] : 0.f;
+      } else if constexpr (EPI == Epi::kPost) {
+        const float ps = post_scale[dst];
+#pragma unroll
+        for (int j = 0; j < EPU; ++j) acc[j] = scale_stored<ST>(acc[j], ps);
       }
       if constexpr (FINAL) store_vec(final_out + (int64_t)dst * ld + col0, acc);
       else store_vec(o, acc);
@@ -239,11 +258,18 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(
       row_accum_tail<T, W>(acc, x, ld, col0, nvalid, colidx, weight,
                            rowptr[row], rowptr[row + 1]);
       const float s = deg_dst ? deg_dst[dst] : 1.f;
+      for (int j = 0; j < nvalid; ++j) {
+        acc[j] *= s;
+        if constexpr (EPI == Epi::kRelu)
+          acc[j] = acc[j] > 0.f ? acc[j] : 0.f;
+        else if constexpr (EPI == Epi::kPost)
+          acc[j] = scale_stored<ST>(acc[j], post_scale[dst]);
+      }
       if constexpr (FINAL) {
         unsigned short* fo = final_out + (int64_t)dst * ld + col0;
-        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, fo + j);
+        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j], fo + j);
       } else {
-        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j] * s, o + j);
+        for (int j = 0; j < nvalid; ++j) f32_to_elt(acc[j], o + j);
       }
     }
   }
@@ -294,10 +320,11 @@ struct StripPass {
   unsigned short* final_out = nullptr;
   const int* out_rows = nullptr;  // plan position -> destination row
   int n_out = 0;                  // rows of the destination
+  const float* post_scale = nullptr;  // Epi::kPost factor, per destination
 };
 
 template <typename T, typename OT, int UN, Weight W, bool HEAVY = false,
-          bool FINAL = false, bool PERM = false>
+          bool FINAL = false, bool PERM = false, Epi EPI = Epi::kNone>
 void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
                  const int* colidx, const float* deg_dst, const float* weight,
                  const c10::optional<torch::Tensor>& row_order, int num_rows,
@@ -313,11 +340,11 @@ void launch_spmm(OT* out, const T* x, const int64_t* rowptr,
   dispatch_gather(g, [&](auto team_c, auto buf_c) {
     hipLaunchKernelGGL(
         (spmm_kernel<T, OT, decltype(team_c)::value, UN,
-                     decltype(buf_c)::value, W, HEAVY, FINAL, PERM>),
+                     decltype(buf_c)::value, W, HEAVY, FINAL, PERM, EPI>),
         g.grid, dim3(kBlock), 0, stream, out, x, rowptr, colidx, deg_dst,
         weight, order, num_rows, ld, col_base, col_end, accumulate, g.bytes,
         sp.heavy_rows, sp.num_heavy, sp.heavy_min, sp.final_out, sp.out_rows,
-        sp.n_out);
+        sp.n_out, sp.post_scale);
   });
 }
 
@@ -443,7 +470,8 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
           int64_t col_base, int64_t ncols,
           c10::optional<torch::Tensor> heavy_rows, int64_t heavy_min,
           c10::optional<torch::Tensor> final_out,
-          c10::optional<torch::Tensor> out_rows) {
+          c10::optional<torch::Tensor> out_rows, bool relu,
+          c10::optional<torch::Tensor> post_scale) {
   check_mat_pair(out, "out", x, "x", "spmm");
   // strip-pass extras: heavy-first schedule and fused final bf16 store
   StripPass sp;
@@ -511,6 +539,28 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
     TORCH_CHECK(!deg_dst.has_value() || deg_dst->numel() == sp.n_out,
                 "spmm: deg_dst must have one entry per destination row");
   }
+  // store epilogues of a finished row: ReLU, or a double-rounded row scale
+  Epi epi = Epi::kNone;
+  if (relu || post_scale.has_value()) {
+    TORCH_CHECK(!(relu && post_scale.has_value()),
+                "spmm: relu and post_scale are exclusive");
+    TORCH_CHECK(!deg_src.has_value() && col_base == 0 && ncols == 0 &&
+                    (final_out.has_value() ||
+                     (out.scalar_type() == x.scalar_type() && !accumulate)),
+                "spmm: relu / post_scale need a whole-row pass that stores "
+                "finished rows, no deg_src");
+    epi = relu ? Epi::kRelu : Epi::kPost;
+    if (post_scale.has_value()) {
+      ROC_CHECK_DEV_CONT(*post_scale);
+      const int64_t n_dst = final_out.has_value() ? final_out->size(0)
+                                                  : out.size(0);
+      TORCH_CHECK(post_scale->scalar_type() == torch::kFloat32 &&
+                      post_scale->numel() == n_dst,
+                  "spmm: post_scale must be fp32, one entry per "
+                  "destination row");
+      sp.post_scale = post_scale->data_ptr<float>();
+    }
+  }
   // column-phase pass: touch only [col_base, col_base+ncols) of every
   // row (ncols == 0 -> the whole row). The stride stays D.
   const int64_t col_end = ncols > 0 ? col_base + ncols : D;
@@ -528,14 +578,36 @@ void spmm(torch::Tensor out, torch::Tensor x, torch::Tensor rowptr,
         auto go = [&](auto un_c, auto w_c) {
           constexpr int UN = decltype(un_c)::value;
           constexpr Weight W = decltype(w_c)::value;
-          auto launch = [&](auto heavy_c, auto final_c, auto perm_c) {
+          auto launch_epi = [&](auto heavy_c, auto final_c, auto perm_c,
+                                auto epi_c) {
             launch_spmm<T, OT, UN, W, decltype(heavy_c)::value,
-                        decltype(final_c)::value, decltype(perm_c)::value>(
+                        decltype(final_c)::value, decltype(perm_c)::value,
+                        decltype(epi_c)::value>(
                 (OT*)out.data_ptr(), (const T*)x.data_ptr(),
                 rowptr.data_ptr<int64_t>(), colidx.data_ptr<int>(),
                 opt_ptr<float>(deg_dst), ds, row_order, num_rows, D,
                 col_base, col_end, accumulate, (size_t)x.numel(),
                 kn.team_override, "spmm", stream, sp);
+          };
+          // the store epilogues exist where finished rows are stored with
+          // no weight (checked above): final passes and OT == T passes
+          auto launch = [&](auto heavy_c, auto final_c, auto perm_c) {
+            if constexpr (W == Weight::kNone &&
+                          (decltype(final_c)::value ||
+                           std::is_same_v<OT, T>)) {
+              if (epi == Epi::kRelu) {
+                launch_epi(heavy_c, final_c, perm_c,
+                           std::integral_constant<Epi, Epi::kRelu>{});
+                return;
+              }
+              if (epi == Epi::kPost) {
+                launch_epi(heavy_c, final_c, perm_c,
+                           std::integral_constant<Epi, Epi::kPost>{});
+                return;
+              }
+            }
+            launch_epi(heavy_c, final_c, perm_c,
+                       std::integral_constant<Epi, Epi::kNone>{});
           };
           // the strip-pass variants exist for bf16 -> fp32, no weight only
           // (checked above), so nothing else is instantiated with them

@@ -10,11 +10,13 @@ serially, `optimizer_kernel.cu:88-94`).
 """
 from __future__ import annotations
 
+import copy
 import time
 
 import torch
 import torch.distributed as dist
 
+from .graph import MASK_TRAIN
 from .ops import functional as F
 from .optim import AdamOptimizer
 from .parallel.partition import GraphShard
@@ -41,8 +43,6 @@ class Trainer:
                              "halo and allgather paths gather bf16 rows")
         self.gather_dtype = gather_dtype
         self.model = model.to(device)
-        self.shard = shard.to(device)
-        self.shard.gather_dtype = gather_dtype
         self.device = torch.device(device)
         self.dtype = compute_dtype
         self.group = group
@@ -54,6 +54,7 @@ class Trainer:
         self.x = feats[lo:hi].to(device=device, dtype=compute_dtype).contiguous()
         self.labels = labels[lo:hi].to(device=device).contiguous()
         self.mask = mask[lo:hi].to(device=device, dtype=torch.int32).contiguous()
+        self.shard = self._place_shard(shard, mask[lo:hi], device)
         self.optimizer = optimizer
         optimizer.setup_flat_grads()  # single-buffer grads (one all-reduce)
         self.num_classes = num_classes  # true classes if logits are padded
@@ -61,6 +62,18 @@ class Trainer:
         self.epoch = 0
         F.set_dropout_seed(seed + shard.rank * 7919)
         self.tracer = None  # set via enable_tracing()
+
+    def _place_shard(self, shard, mask, device):
+        """The shard on the device, with the transpose plan of this
+        trainer's loss rows: _forward_loss feeds the model's output to
+        softmax_cross_entropy with this mask, whose gradient is zero on
+        every row that is not a training row, for as long as the mask
+        stays (models pass loss_rows_only=True on their last aggregation)."""
+        shard = copy.copy(shard)  # the caller's shard keeps its plans
+        shard.install_loss_rows(mask == MASK_TRAIN)
+        shard = shard.to(device)
+        shard.gather_dtype = self.gather_dtype
+        return shard
 
     def enable_tracing(self):
         from .utils.trace import Tracer
@@ -322,9 +335,8 @@ class Trainer:
 
     def load_shard(self, shard, feats, labels, mask, local_slices=False):
         device, dt = self.device, self.dtype
-        self.shard = shard.to(device)
-        self.shard.gather_dtype = self.gather_dtype
         lo, hi = (0, shard.n_local) if local_slices else (shard.lo, shard.hi)
+        self.shard = self._place_shard(shard, mask[lo:hi], device)
         self.x = feats[lo:hi].to(device=device, dtype=dt).contiguous()
         self.labels = labels[lo:hi].to(device=device).contiguous()
         self.mask = mask[lo:hi].to(device=device,

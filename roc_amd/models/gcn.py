@@ -22,7 +22,7 @@ import torch
 from ..ops import functional as F
 from ..ops.reference import glorot_uniform
 from ..parallel.halo import halo_exchange
-from ..parallel.aggregate import aggregate
+from ..parallel.aggregate import aggregate, fuses_grad_src_scale
 from .norm import make_norm_params, hidden_act, norm_parameters
 
 
@@ -89,11 +89,24 @@ class GCN(torch.nn.Module):
                 # rank scales its rows BEFORE the halo exchange);
                 # dst-side D^-1/2 rides the SpMM store. No per-edge
                 # degree gather.
-                h = F.linear(h, w, row_scale=shard.rsqrt_deg_local)
+                # Backward, the transpose SpMM stores the gradient with
+                # that source factor already on it where it can, and the
+                # linear then skips its own scaling pass. The hidden
+                # layers' plain ReLU rides the SpMM's store. The last
+                # layer's output is the logits, whose gradient is zero
+                # outside the trainer's loss rows.
+                last = i == len(self.weights) - 1
+                fuse = fuses_grad_src_scale(shard, **drop)
+                act = not last and self.norm == "none"
+                rs = shard.rsqrt_deg_local
+                h = F.linear(h, w, row_scale=rs, grad_prescaled=fuse)
                 # strategy (halo a2a / overlap / all_gather) is the
                 # shard's choice — see parallel/aggregate.py
-                h = aggregate(h, shard, dst_scale=shard.rsqrt_deg_local,
-                              group=group, **drop)
+                h = aggregate(h, shard, dst_scale=rs, group=group, relu=act,
+                              grad_src_scale=rs if fuse else None,
+                              loss_rows_only=last, **drop)
+                if act:
+                    return self._residual(h, x, i)
         else:
             h = F.linear(h, w)
             h = halo_exchange(h, shard, group)
@@ -103,6 +116,9 @@ class GCN(torch.nn.Module):
                 shard)
         if i < len(self.weights) - 1:
             h = hidden_act(self, i, h, shard, group)
+        return self._residual(h, x, i)
+
+    def _residual(self, h, x, i):
         if self.residual:
             proj = self.res_proj[i]
             if proj.numel() > 0:

@@ -125,27 +125,32 @@ def _spmm_launcher(fp8_scale):
 
     def run(out, q, rowptr, colidx, deg_dst=None, deg_src=None,
             row_order=None, accumulate=False, col_base=0, ncols=0,
-            heavy_rows=None, heavy_min=0, final_out=None, out_rows=None):
+            heavy_rows=None, heavy_min=0, final_out=None, out_rows=None,
+            relu=False, post_scale=None):
         assert deg_src is None and col_base == 0 and ncols == 0
+        assert not relu and post_scale is None, \
+            "fp8 passes have no store epilogues"
         _C.spmm_fp8(out, q, fp8_scale, rowptr, colidx, deg_dst, row_order,
                     accumulate, heavy_rows, heavy_min, final_out, out_rows)
     return run
 
 
 def _strip_spmm_ordered(x, strips, num_rows, row_scale, order,
-                        fp8_scale=None):
+                        fp8_scale=None, relu=False, post_scale=None):
     """The strip SpMM on a degree-ordered plan
     (partition.build_strip_plan_ordered): the light rows in one plain
     pass, then the heavy region's K-1 accumulate passes over fp32 partials
     kept in plan order, then its final pass; the light and the final pass
-    store their bf16 rows through the plan's permutation into one out."""
+    store their bf16 rows through the plan's permutation into one out.
+    relu / post_scale ride those two stores (see _strip_spmm)."""
     perm_heavy, perm_light, lrp, lci = order
+    epi = (relu, post_scale) if relu or post_scale is not None else ()
     D = x.shape[1]
     spmm = _spmm_launcher(fp8_scale)
     out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
     if perm_light.numel():
         spmm(out, x, lrp, lci, row_scale, None, None, False, 0, 0, None,
-             0, None, perm_light)
+             0, None, perm_light, *epi)
     n_heavy = perm_heavy.numel()
     if n_heavy:
         out32 = torch.empty(n_heavy, D, dtype=torch.float32, device=x.device)
@@ -155,12 +160,12 @@ def _strip_spmm_ordered(x, strips, num_rows, row_scale, order,
                 spmm(out32, x, srp, sci, None, None, None, i > 0)
             else:
                 spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
-                     0, 0, None, 0, out, perm_heavy)
+                     0, 0, None, 0, out, perm_heavy, *epi)
     return out
 
 
 def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
-                order=None, fp8_scale=None):
+                order=None, fp8_scale=None, relu=False, post_scale=None):
     """Source-strip-blocked SpMM: each pass gathers from an L2-resident
     source window; partials accumulate in fp32 (one rounding total —
     same numerics as single-pass). Wide feature dims additionally sweep
@@ -175,14 +180,19 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
     order: the strips are a degree-ordered plan (_strip_spmm_ordered).
     fp8_scale: x is the e4m3 bytes of quantize_rows_fp8 and this its scale
     vector; the passes are the bf16 whole-row ones on the fp8 kernel (no
-    column phases: the caller takes the one-pass kernel when they are on)."""
+    column phases: the caller takes the one-pass kernel when they are on).
+    relu: the result is max(0, .) of the scaled sum. post_scale: a second
+    fp32 row factor applied to the *stored* result, that is rounded twice,
+    exactly as a rowscale pass over the output would. Both ride the store of
+    the last bf16 pass; the other epilogues run them as passes of their own."""
     fp8 = fp8_scale is not None
+    epi = (relu, post_scale) if relu or post_scale is not None else ()
     assert not (fp8 and _phase_cols()), "fp8 strip passes: whole rows only"
     if order is not None:
         assert fp8 or _order_applies(x), \
             "ordered strip plan: whole-row bf16 only"
         return _strip_spmm_ordered(x, strips, num_rows, row_scale, order,
-                                   fp8_scale)
+                                   fp8_scale, relu, post_scale)
     spmm = _spmm_launcher(fp8_scale)
     D = x.shape[1]
     out32 = torch.empty(num_rows, D, dtype=torch.float32, device=x.device)
@@ -203,7 +213,7 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
                 out = torch.empty(num_rows, D, dtype=torch.bfloat16,
                                   device=x.device)
                 spmm(out32, x, srp, sci, row_scale, None, None, i > 0,
-                     0, 0, hv, heavy_min, out)
+                     0, 0, hv, heavy_min, out, None, *epi)
             else:
                 spmm(out32, x, srp, sci, None, None, None, i > 0,
                      col_base, ncols, hv, heavy_min)
@@ -212,10 +222,19 @@ def _strip_spmm(x, strips, num_rows, row_scale, heavy=None, heavy_min=0,
     if x.dtype == torch.bfloat16 and D % 8 == 0:
         out = torch.empty(num_rows, D, dtype=torch.bfloat16, device=x.device)
         _C.cast_rowscale(out, out32, row_scale)  # fused epilogue
-        return out
-    if row_scale is not None:
-        out32 = out32 * row_scale.unsqueeze(1)
-    return out32.to(x.dtype)
+    else:
+        if row_scale is not None:
+            out32 = out32 * row_scale.unsqueeze(1)
+        out = out32.to(x.dtype)
+    if relu:  # the maps take restrict pointers: never in place
+        act = torch.empty_like(out)
+        _C.relu_fwd(act, out)
+        out = act
+    if post_scale is not None:
+        scaled = torch.empty_like(out)
+        _C.rowscale(scaled, out, post_scale)
+        out = scaled
+    return out
 
 
 class _SpMM(torch.autograd.Function):
@@ -227,18 +246,32 @@ class _SpMM(torch.autograd.Function):
     def forward(ctx, x, rowptr, colidx, t_rowptr, t_colidx, num_rows, num_ext,
                 deg_dst, deg_src, row_order, t_row_order,
                 fwd_strips=None, bwd_strips=None, fwd_heavy=None,
-                bwd_heavy=None, heavy_min=0, fwd_order=None, bwd_order=None):
-        ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src, t_row_order)
+                bwd_heavy=None, heavy_min=0, fwd_order=None, bwd_order=None,
+                relu=False, grad_src_scale=None, bwd_loss=None):
+        # relu: out = max(0, .), and the backward masks dy by it.
+        # grad_src_scale: fp32 [num_ext], multiplied into the stored dx the
+        # way a rowscale pass over it would (the consumer's own backward
+        # row scaling, handed over).
+        # bwd_loss: (strips, heavy, keep) of GraphShard.install_loss_rows;
+        # the caller guarantees dy is zero outside keep.
         ctx.num_ext = num_ext
         ctx.bwd_strips = bwd_strips
         ctx.bwd_heavy = (bwd_heavy, heavy_min, bwd_order)
+        ctx.bwd_loss = bwd_loss
+        ctx.relu = relu
         if (_hip(x) and fwd_strips is not None and deg_src is None
                 and (fwd_order is None or _order_applies(x))):
             out = _strip_spmm(x, fwd_strips, num_rows, deg_dst, fwd_heavy,
-                              heavy_min, fwd_order)
+                              heavy_min, fwd_order, relu=relu)
         elif _hip(x):
             out = torch.empty(num_rows, x.shape[1], dtype=x.dtype, device=x.device)
-            _C.spmm(out, x, rowptr, colidx, deg_dst, deg_src, row_order)
+            fuse = relu and deg_src is None
+            _C.spmm(out, x, rowptr, colidx, deg_dst, deg_src, row_order,
+                    relu=fuse)
+            if relu and not fuse:
+                act = torch.empty_like(out)
+                _C.relu_fwd(act, out)
+                out = act
         else:
             xin = x
             if deg_src is not None:  # deg_* are precomputed row scale factors
@@ -246,36 +279,84 @@ class _SpMM(torch.autograd.Function):
             out = ref.spmm(xin, rowptr, colidx, num_rows)
             if deg_dst is not None:
                 out = out * deg_dst.unsqueeze(1).to(out.dtype)
+            if relu:
+                out = ref.relu(out)
+        ctx.save_for_backward(t_rowptr, t_colidx, deg_dst, deg_src,
+                              t_row_order, grad_src_scale,
+                              out if relu else None)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        t_rowptr, t_colidx, deg_dst, deg_src, t_row_order = ctx.saved_tensors
+        (t_rowptr, t_colidx, deg_dst, deg_src, t_row_order, gss,
+         y) = ctx.saved_tensors
         dy = dy.contiguous()
         # d/dx of  diag(a) A diag(b) x  =  diag(b) A^T diag(a) dy
         if _hip(dy):
-            if deg_dst is not None:
+            if ctx.relu:
+                # the ReLU mask and the pre-scale below in one pass
+                tmp = torch.empty_like(dy)
+                _C.relu_bwd(tmp, dy, y, deg_dst)
+                dy = tmp
+            elif deg_dst is not None:
                 # pre-scale the gradient rows ONCE (one cheap pass) instead
                 # of a per-edge deg gather inside the transpose SpMM
                 tmp = torch.empty_like(dy)
                 _C.rowscale(tmp, dy, deg_dst)
                 dy = tmp
-            if (ctx.bwd_strips is not None and deg_src is None
+            if ctx.bwd_strips is not None and deg_src is None \
+                    and ctx.bwd_loss is not None:
+                strips, heavy, keep = ctx.bwd_loss
+                _debug_check_loss_rows(dy, keep)
+                dx = _strip_spmm(dy, strips, ctx.num_ext, None, heavy,
+                                 ctx.bwd_heavy[1], post_scale=gss)
+            elif (ctx.bwd_strips is not None and deg_src is None
                     and (ctx.bwd_heavy[2] is None or _order_applies(dy))):
                 dx = _strip_spmm(dy, ctx.bwd_strips, ctx.num_ext, None,
-                                 *ctx.bwd_heavy)
+                                 *ctx.bwd_heavy, post_scale=gss)
             else:
                 dx = torch.empty(ctx.num_ext, dy.shape[1], dtype=dy.dtype,
                                  device=dy.device)
-                _C.spmm(dx, dy, t_rowptr, t_colidx, deg_src, None, t_row_order)
+                fuse = gss if deg_src is None else None
+                _C.spmm(dx, dy, t_rowptr, t_colidx, deg_src, None, t_row_order,
+                        post_scale=fuse)
+                if gss is not None and fuse is None:
+                    scaled = torch.empty_like(dx)
+                    _C.rowscale(scaled, dx, gss)
+                    dx = scaled
         else:
             yin = dy
+            if ctx.relu:
+                yin = ref.relu_grad(yin, y)
             if deg_dst is not None:
                 yin = yin * deg_dst.unsqueeze(1).to(yin.dtype)
             dx = ref.spmm(yin, t_rowptr, t_colidx, ctx.num_ext)
             if deg_src is not None:
                 dx = dx * deg_src.unsqueeze(1).to(dx.dtype)
-        return (dx,) + (None,) * 17
+            if gss is not None:
+                dx = dx * gss.unsqueeze(1).to(dx.dtype)
+        return (dx,) + (None,) * 20
+
+
+_DEBUG_LOSS_ROWS = None
+
+
+def _debug_check_loss_rows(dy, keep) -> None:
+    """ROC_DEBUG_LOSS_ROWS=1: before a pruned transpose plan is used, check
+    what its caller guarantees, that dy is zero on every row outside the
+    keep-vector. A violation would silently lose gradient. Eager only: the
+    check reads the device, so it never runs under stream capture."""
+    global _DEBUG_LOSS_ROWS
+    if _DEBUG_LOSS_ROWS is None:
+        import os
+        _DEBUG_LOSS_ROWS = os.environ.get("ROC_DEBUG_LOSS_ROWS", "0") == "1"
+    if not _DEBUG_LOSS_ROWS or torch.cuda.is_current_stream_capturing():
+        return
+    bad = (dy[~keep] != 0).any(dim=1)
+    if bool(bad.any()):
+        raise RuntimeError(
+            f"loss_rows_only: {int(bad.sum())} gradient rows outside the "
+            "shard's loss rows are nonzero")
 
 
 def quantize_rows_fp8(x, pre_scale=None):
@@ -605,7 +686,9 @@ def attention_softmax(s_src, s_dst, shard, slope: float = 0.2):
 
 def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
                    src_scale=None, gather_dtype=None, edge_drop: float = 0.0,
-                   training: bool = False, edge_call_id=None):
+                   training: bool = False, edge_call_id=None,
+                   relu: bool = False, grad_src_scale=None,
+                   loss_rows_only: bool = False):
     """Neighbor sum-aggregation over the shard's local CSR.
 
     x: [n_ext, D] halo-extended features. Returns [n_local, D].
@@ -638,6 +721,17 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
     are not used with it (a strip plan of the drop kernel is the follow-up),
     and it does not combine with gather_dtype="fp8" (raises; a shard-level
     fp8 preference gives way). docs/KERNELS.md, spmm_drop, has the numbers.
+    relu=True returns max(0, .) of the result, in the store of the SpMM, and
+    the backward masks the gradient by it (with the dst pre-scale, one pass).
+    grad_src_scale: fp32 [n_ext]; the gradient w.r.t. x comes back multiplied
+    by it per row, rounded as a rowscale pass over the stored gradient would
+    round (the producer of x then skips that pass: linear(grad_prescaled=
+    True)). loss_rows_only=True is the caller's promise that the incoming
+    gradient is zero outside the rows the shard's loss-row plan was built
+    for (GraphShard.install_loss_rows); the backward then skips those
+    columns of the transpose. Without such a plan it changes nothing. All
+    three belong to the plain bf16/fp32 path: the DropEdge and fp8 paths
+    take none of them (relu / grad_src_scale raise there).
     """
     deg_dst = shard.rsqrt_deg_local if normalize else dst_scale
     deg_src = shard.rsqrt_deg_ext if normalize else src_scale
@@ -645,6 +739,9 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
         if gather_dtype == "fp8":
             raise ValueError("scatter_gather: edge_drop > 0 does not combine "
                              "with gather_dtype='fp8'")
+        if relu or grad_src_scale is not None:
+            raise ValueError("scatter_gather: relu / grad_src_scale do not "
+                             "combine with edge_drop")
         return scatter_gather_drop_csr(
             x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
             shard.n_local, shard.n_ext, edge_drop, deg_dst, deg_src,
@@ -662,6 +759,17 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
         raise ValueError(
             "scatter_gather: gather_dtype='fp8' needs bf16 x with D % 16 == 0 "
             f"and D <= 1024, got {x.dtype} {tuple(x.shape)}")
+    extra = ()
+    if gather_dtype == "fp8":
+        if relu or grad_src_scale is not None:
+            raise ValueError("scatter_gather: relu / grad_src_scale do not "
+                             "combine with gather_dtype='fp8'")
+    else:
+        loss = None
+        if loss_rows_only and getattr(shard, "bwd_loss_strips", None):
+            loss = (shard.bwd_loss_strips, shard.bwd_loss_heavy,
+                    shard.loss_keep)
+        extra = (relu, grad_src_scale, loss)
     op = _SpMMFp8 if gather_dtype == "fp8" else _SpMM
     return op.apply(
         x, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
@@ -673,6 +781,7 @@ def scatter_gather(x, shard, normalize: bool = False, dst_scale=None,
         getattr(shard, "strip_heavy_min", 0),
         getattr(shard, "fwd_strip_order", None),
         getattr(shard, "bwd_strip_order", None),
+        *extra,
     )
 
 
@@ -1463,7 +1572,10 @@ class _Linear(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, w, act, row_scale):
+    def forward(ctx, x, w, act, row_scale, grad_prescaled=False):
+        # grad_prescaled: dy arrives with row_scale already applied (the
+        # consumer's backward stored it so: scatter_gather grad_src_scale)
+        ctx.grad_prescaled = grad_prescaled
         if _hip(x):
             # gemm_rr takes B pre-transposed: Bt = w^T [out,in]
             wt, wc = _cast_weight(w, x.dtype)
@@ -1498,7 +1610,7 @@ class _Linear(torch.autograd.Function):
                 dym = torch.empty_like(dy)
                 _C.sigmoid_bwd(dym, dy, y)
                 dy = dym
-            if row_scale is not None:
+            if row_scale is not None and not ctx.grad_prescaled:
                 dym = torch.empty_like(dy)
                 _C.rowscale(dym, dy, row_scale)
                 dy = dym
@@ -1533,17 +1645,22 @@ class _Linear(torch.autograd.Function):
                 dy = ref.relu_grad(dy, y)
             elif act == "sigmoid":
                 dy = ref.sigmoid_grad(dy, y)
-            if row_scale is not None:
+            if row_scale is not None and not ctx.grad_prescaled:
                 dy = dy * row_scale.unsqueeze(1).to(dy.dtype)
             dw = (x.to(torch.float32).t() @ dy.to(torch.float32))
             dx = (dy @ w.t().to(dy.dtype)) if ctx.needs_input_grad[0] else None
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
-def linear(x, w, activation: Optional[str] = None, row_scale=None):
+def linear(x, w, activation: Optional[str] = None, row_scale=None,
+           grad_prescaled: bool = False):
     """y = act((x @ w) * row_scale). row_scale rides the GEMM epilogue
-    (used for the GCN source-degree pre-normalization)."""
-    return _Linear.apply(x, w, activation, row_scale)
+    (used for the GCN source-degree pre-normalization).
+    grad_prescaled=True: the gradient that comes back for y already carries
+    row_scale (scatter_gather(grad_src_scale=row_scale) is y's only
+    consumer), so the backward does not apply it again. The forward is the
+    same either way."""
+    return _Linear.apply(x, w, activation, row_scale, grad_prescaled)
 
 
 # ---------------------------------------------------------------------------

@@ -257,9 +257,20 @@ def _aggregate_drop(x, shard, dst_scale, group, p, call_id):
                              training=True, edge_call_id=call_id)
 
 
+def fuses_grad_src_scale(shard, edge_drop: float = 0.0,
+                         training: bool = False, **_) -> bool:
+    """Whether aggregate(reduce="sum", grad_src_scale=...) with these
+    arguments applies the factor itself: the single-process bf16/fp32 path,
+    where the gradient w.r.t. x leaves the transpose SpMM as x's own rows.
+    A model asks before it tells its linear grad_prescaled=True."""
+    return (shard.world_size == 1 and not (training and edge_drop > 0.0)
+            and getattr(shard, "gather_dtype", None) != "fp8")
+
+
 def aggregate(x, shard, dst_scale=None, group=None, reduce="sum",
               edge_drop: float = 0.0, training: bool = False,
-              edge_call_id=None, temperature=None):
+              edge_call_id=None, temperature=None, relu: bool = False,
+              grad_src_scale=None, loss_rows_only: bool = False):
     """Distributed neighbor aggregation of the LOCAL feature block.
     Returns [n_local, D]. reduce="sum" (+ optional fused dst-side degree
     scale) is the sum / mean path; reduce="max" | "min" takes the
@@ -277,22 +288,44 @@ def aggregate(x, shard, dst_scale=None, group=None, reduce="sum",
     edge_drop=p with training=True (reduce="sum" only) is DropEdge, see
     ops.functional.scatter_gather; it too exchanges first and aggregates
     after, over the local ids of the shard (the gather-space ids in
-    allgather mode), so every partitioning draws its own mask."""
+    allgather mode), so every partitioning draws its own mask.
+    relu=True closes the sum with max(0, .); the single-process path does
+    it in the SpMM's store (ops.functional.scatter_gather), every other
+    path as the activation pass it replaces. grad_src_scale and
+    loss_rows_only are scatter_gather's: the first is accepted only where
+    fuses_grad_src_scale() says so, the second is a promise about the
+    incoming gradient that paths without a loss-row plan ignore."""
     from ..ops import functional as Fn
+    if grad_src_scale is not None and (
+            reduce != "sum" or not fuses_grad_src_scale(
+                shard, edge_drop, training)):
+        raise ValueError("grad_src_scale: this path does not scale the "
+                         "gradient (ask fuses_grad_src_scale first)")
     if training and edge_drop > 0.0:
         if reduce != "sum":
             raise ValueError("edge_drop applies to reduce='sum' only")
-        return _aggregate_drop(x, shard, dst_scale, group, edge_drop,
-                               edge_call_id)
+        out = _aggregate_drop(x, shard, dst_scale, group, edge_drop,
+                              edge_call_id)
+        return Fn.relu(out) if relu else out
     if reduce != "sum":
         if dst_scale is not None:
             raise ValueError("dst_scale applies to reduce='sum' only")
+        if relu:
+            raise ValueError("relu applies to reduce='sum' only")
         return _aggregate_reduce(x, shard, reduce, group, temperature)
     if shard.world_size == 1:
-        return Fn.scatter_gather(x, shard, dst_scale=dst_scale)
+        if getattr(shard, "gather_dtype", None) == "fp8":
+            out = Fn.scatter_gather(x, shard, dst_scale=dst_scale)
+            return Fn.relu(out) if relu else out
+        return Fn.scatter_gather(x, shard, dst_scale=dst_scale, relu=relu,
+                                 grad_src_scale=grad_src_scale,
+                                 loss_rows_only=loss_rows_only)
     if shard.comm_mode == "allgather":
-        return _GatherAggregate.apply(x, shard, dst_scale, group)
-    if overlap_enabled() and shard.has_overlap_split:
-        return halo_aggregate(x, shard, dst_scale=dst_scale, group=group)
-    xe = halo_exchange(x, shard, group)
-    return Fn.scatter_gather(xe, shard, dst_scale=dst_scale)
+        out = _GatherAggregate.apply(x, shard, dst_scale, group)
+    elif overlap_enabled() and shard.has_overlap_split:
+        out = halo_aggregate(x, shard, dst_scale=dst_scale, group=group)
+    else:
+        xe = halo_exchange(x, shard, group)
+        out = Fn.scatter_gather(xe, shard, dst_scale=dst_scale,
+                                loss_rows_only=loss_rows_only)
+    return Fn.relu(out) if relu else out

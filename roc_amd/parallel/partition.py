@@ -114,6 +114,12 @@ class GraphShard:
     # heavy lists. None = natural plan.
     fwd_strip_order: Optional[list] = None
     bwd_strip_order: Optional[list] = None
+    # transpose plan without the columns (local rows) that carry no loss
+    # (install_loss_rows): natural strips, their heavy lists, and the bool
+    # keep-vector [n_local] it was built for. None = not installed.
+    bwd_loss_strips: Optional[list] = None
+    bwd_loss_heavy: Optional[list] = None
+    loss_keep: Optional[torch.Tensor] = None
     # how ops.functional.scatter_gather gathers feature rows by default:
     # None / "bf16" = as stored, "fp8" = e4m3 rows with per-row scales
     # (world size 1 only; engine.Trainer sets it)
@@ -132,6 +138,30 @@ class GraphShard:
                 v = [t.to(device) for t in v]
             d[k] = v
         return GraphShard(**d)
+
+    def install_loss_rows(self, keep: torch.Tensor) -> bool:
+        """Build the loss-row-pruned transpose plan for `keep` (bool
+        [n_local]: the rows whose output gradient can be nonzero) on a
+        shard that still lives on the host; .to() uploads it with the other
+        plans. A caller that passes loss_rows_only=True to scatter_gather
+        guarantees that the gradient rows outside `keep` are zero. Built
+        only where the ordinary backward strip plan exists (and
+        ROC_SPMM_LOSS_ROWS is not 0); returns whether it was."""
+        self.bwd_loss_strips = self.bwd_loss_heavy = self.loss_keep = None
+        on, width = loss_rows_knobs()
+        if not on or self.bwd_strips is None or self.bwd_strip_order is not None:
+            return False
+        keep = keep.to(device="cpu", dtype=torch.bool).contiguous()
+        assert keep.numel() == self.n_local, "keep: one entry per local row"
+        strips, _ = build_loss_strip_plan(self.t_rowptr.cpu(),
+                                          self.t_colidx.cpu(), keep, width)
+        dev = self.t_rowptr.device
+        if self.strip_heavy_min > 0:
+            self.bwd_loss_heavy = [h.to(dev) for h in build_strip_heavy(
+                strips, self.strip_heavy_min)]
+        self.bwd_loss_strips = [(a.to(dev), b.to(dev)) for a, b in strips]
+        self.loss_keep = keep.to(dev)
+        return True
 
     @property
     def has_overlap_split(self) -> bool:
@@ -210,16 +240,22 @@ def build_strip_plan(rowptr: torch.Tensor, colidx: torch.Tensor,
     1.39x faster than one pass — sources stay L2-resident per strip.
     Partials accumulate in an fp32 buffer (mixed-output kernel), so
     numerics are exactly one rounding, same as single-pass."""
-    rp = rowptr.numpy()
-    ci = colidx.numpy()
+    return _strip_plan_at(rowptr.numpy(), colidx.numpy(), num_cols,
+                          range(width, num_cols, width))
+
+
+def _strip_plan_at(rp: np.ndarray, ci: np.ndarray, num_cols: int, cuts):
+    """The strip CSRs of a CSR with sorted rows for the ascending interior
+    column boundaries `cuts`: strip s holds the columns in
+    [cuts[s-1], cuts[s]), the first from 0 and the last up to num_cols."""
     nrows = rp.shape[0] - 1
     ci64 = ci.astype(np.int64)
     row = np.repeat(np.arange(nrows, dtype=np.int64), np.diff(rp))
     key = row * (num_cols + 1) + ci64
     rows_q = np.arange(nrows, dtype=np.int64) * (num_cols + 1)
     pos = [rp[:-1].astype(np.int64)]
-    for b in range(width, num_cols, width):
-        pos.append(np.searchsorted(key, rows_q + b))
+    for b in cuts:
+        pos.append(np.searchsorted(key, rows_q + int(b)))
     pos.append(rp[1:].astype(np.int64))
     strips = []
     for s in range(len(pos) - 1):
@@ -268,6 +304,58 @@ def build_strip_heavy(strips, heavy_min: int):
         rows = rows[np.argsort(-seg[rows], kind="stable")]
         heavy.append(torch.from_numpy(rows.astype(np.int32)))
     return heavy
+
+
+# Live-column window of the loss-row-pruned transpose plan. Swept at the
+# Reddit shape, D=64 (profiles/r49): 16384 0.78 ms, 24576 0.71, 32768 0.68,
+# 49152 0.68, 65536 0.76 against 1.14 for the full plan. A 128-B row is
+# one cache line, so a window twice the other plans' still stays cached.
+LOSS_WIDTH_DEFAULT = 32768
+_LOSS_ROWS: Optional[tuple] = None
+
+
+def loss_rows_knobs() -> tuple:
+    """(on, width): whether a trainer's loss rows get a pruned transpose
+    plan (ROC_SPMM_LOSS_ROWS, 1/0) and how many live columns one of its
+    windows holds (ROC_SPMM_LOSS_WIDTH). Pinned at first use."""
+    global _LOSS_ROWS
+    if _LOSS_ROWS is None:
+        _LOSS_ROWS = (
+            os.environ.get("ROC_SPMM_LOSS_ROWS", "1") != "0",
+            max(1, int(os.environ.get("ROC_SPMM_LOSS_WIDTH",
+                                      str(LOSS_WIDTH_DEFAULT)))))
+    return _LOSS_ROWS
+
+
+def build_loss_strip_plan(rowptr: torch.Tensor, colidx: torch.Tensor,
+                          keep: torch.Tensor, width: int):
+    """Strip plan of a CSR with sorted rows restricted to the columns where
+    `keep` (bool, one entry per column) is set: a transpose SpMM over it
+    equals the full one whenever the dropped columns' rows of the operand
+    are zero (each dropped edge would add +-0 to an fp32 sum that starts at
+    +0). Returns (strips, bounds):
+      strips  as build_strip_plan gives them, over the same rows; only edges
+              with a kept column, in their original order within a row
+      bounds  int64 column ids [0, b_1, ..., num_cols]: strip s covers the
+              columns [bounds[s], bounds[s+1]), cut so that every strip but
+              the last holds exactly `width` kept columns. Dead columns
+              inside a window are never gathered, so they cost no cache.
+    There is always one strip at least (no kept column: one strip with no
+    edges), so the first pass still stores a zero for every row."""
+    rp = rowptr.numpy()
+    ci = colidx.numpy()
+    kp = np.ascontiguousarray(keep.numpy().astype(bool))
+    num_cols = kp.shape[0]
+    live = np.nonzero(kp)[0]
+    cuts = live[width::width]  # column id of every width-th kept column
+    ekeep = kp[ci]
+    before = np.zeros(ci.shape[0] + 1, dtype=np.int64)
+    np.cumsum(ekeep, out=before[1:])
+    krp = before[rp]
+    kci = np.ascontiguousarray(ci[ekeep])
+    strips = _strip_plan_at(krp, kci, num_cols, cuts)
+    bounds = np.concatenate([[0], cuts, [num_cols]]).astype(np.int64)
+    return strips, torch.from_numpy(bounds)
 
 
 _STRIP_ORDER: Optional[bool] = None
