@@ -158,6 +158,14 @@ void att_softmax_bwd(torch::Tensor dsrc, torch::Tensor dsdst,
                      torch::Tensor s_src, torch::Tensor s_dst,
                      torch::Tensor rowptr, torch::Tensor colidx,
                      double slope);
+std::vector<torch::Tensor> sample_hop_device(torch::Tensor rowptr,
+                                             torch::Tensor colidx,
+                                             torch::Tensor targets,
+                                             int64_t fanout, int64_t seed,
+                                             torch::Tensor slot,
+                                             torch::Tensor first);
+void gather_rows_cast(torch::Tensor out, torch::Tensor feats,
+                      torch::Tensor ids);
 void register_graph_cpu(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -384,5 +392,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("att_softmax_fwd", &att_softmax_fwd,
         "fused GAT attention: lrelu(s_src[col]+s_dst[row]) -> softmax");
   m.def("att_softmax_bwd", &att_softmax_bwd);
+  m.def("sample_hop_device", &sample_hop_device,
+        "one neighbour-sampling hop on the device, bit-identical to "
+        "sample_hop + csr_transpose: (rowptr_s, colidx_local, src_ids, "
+        "t_rowptr, t_colidx, t_edge_perm, inv_deg). slot / first are the "
+        "sampler's int32 [N] workspace (-1 / INT_MAX), restored on exit",
+        pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("targets"), pybind11::arg("fanout"),
+        pybind11::arg("seed"), pybind11::arg("slot"), pybind11::arg("first"));
+  m.def("gather_rows_cast", &gather_rows_cast,
+        "out[j, :] = feats[ids[j], :] cast to out's dtype in the store",
+        pybind11::arg("out"), pybind11::arg("feats"), pybind11::arg("ids"));
   register_graph_cpu(m);
 }

@@ -11,10 +11,13 @@
 //
 // Fast path (C <= 64): ONE global read per row — each lane holds one
 // class in a register for max/sum/grad. Metrics accumulate in wave
-// registers across all rows, then one LDS reduction per block and 8
-// global atomics per block (the naive per-row atomic version serialized
-// ~700k adds onto 8 words and cost 7.2 ms/epoch on Reddit — see
-// profiles/r01_baseline_kernel_stats.md).
+// registers across all rows, then fold in a FIXED order: the block's waves
+// through LDS slots into one partial row per block, the partial rows in a
+// small second launch (the naive per-row atomic version serialized ~700k
+// adds onto 8 words and cost 7.2 ms/epoch on Reddit — see
+// profiles/r01_baseline_kernel_stats.md). No float atomics: the same
+// logits give the same loss bits on every run, which the sampled tier's
+// host/device equality rests on.
 // Replaces reference cudnnSoftmaxForward + softmax_backward + calc_loss
 // (`softmax_kernel.cu:19-171`).
 
@@ -27,13 +30,11 @@ constexpr float kNegInf = -3.4e38f;
 
 template <typename T, bool NARROW>
 __global__ __launch_bounds__(kBlock) void softmax_ce_kernel(
-    T* __restrict__ dl, float* __restrict__ metrics,
+    T* __restrict__ dl, float* __restrict__ partials,
     const T* __restrict__ logits, const int64_t* __restrict__ labels,
     const int* __restrict__ mask, float grad_scale, int num_rows, int C,
     int stride) {
-  __shared__ float macc[8];
-  if (threadIdx.x < 8) macc[threadIdx.x] = 0.f;
-  __syncthreads();
+  __shared__ float macc[kBlock / 64][8];
 
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / 64;
   const int lane = threadIdx.x & 63;
@@ -119,14 +120,33 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_kernel(
     }
   }
 
-  // block reduction: one lane per wave -> LDS -> 8 global atomics
+  // block reduction: one lane per wave -> its LDS slot -> the block's
+  // partial row, waves summed in index order
   if (lane == 0) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) atomicAdd(&macc[j], acc[j]);
+    for (int j = 0; j < 8; ++j) macc[threadIdx.x >> 6][j] = acc[j];
   }
   __syncthreads();
-  if (threadIdx.x < 8 && macc[threadIdx.x] != 0.f)
-    atomicAdd(&metrics[threadIdx.x], macc[threadIdx.x]);
+  if (threadIdx.x < 8) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) t += macc[w][threadIdx.x];
+    partials[blockIdx.x * 8 + threadIdx.x] = t;
+  }
+}
+
+// metrics[j] += sum over blocks of partials[b][j]: block j, one wave. Each
+// lane adds its blocks in ascending order, then a butterfly over the lanes,
+// so the order of the additions depends on nblocks alone.
+__global__ __launch_bounds__(64) void softmax_ce_fold_kernel(
+    float* __restrict__ metrics, const float* __restrict__ partials,
+    int nblocks) {
+  const int j = blockIdx.x;
+  float t = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += 64) t += partials[b * 8 + j];
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) t += __shfl_xor(t, w);
+  if (threadIdx.x == 0) metrics[j] += t;
 }
 
 }  // namespace
@@ -148,11 +168,12 @@ void softmax_ce(torch::Tensor dl, torch::Tensor metrics, torch::Tensor logits,
   TORCH_CHECK(C <= stride, "num_classes exceeds logits width");
   const int waves_per_block = kBlock / 64;
   const int grid = roc_grid_1d(n, waves_per_block, 2048);
+  auto partials = torch::empty({grid, 8}, metrics.options());
   auto s = roc_stream();
 #define ROC_SCE(T, NARROW, PT)                                            \
   hipLaunchKernelGGL((softmax_ce_kernel<T, NARROW>), dim3(grid),          \
                      dim3(kBlock), 0, s, (T*)dl.data_ptr(),               \
-                     metrics.data_ptr<float>(), (const T*)logits.data_ptr(), \
+                     partials.data_ptr<float>(), (const T*)logits.data_ptr(), \
                      labels.data_ptr<int64_t>(), mask.data_ptr<int>(),    \
                      (float)grad_scale, n, C, stride)
   if (logits.scalar_type() == torch::kBFloat16) {
@@ -165,5 +186,8 @@ void softmax_ce(torch::Tensor dl, torch::Tensor metrics, torch::Tensor logits,
     TORCH_CHECK(false, "softmax_ce: unsupported dtype");
   }
 #undef ROC_SCE
+  hipLaunchKernelGGL(softmax_ce_fold_kernel, dim3(8), dim3(64), 0, s,
+                     metrics.data_ptr<float>(), partials.data_ptr<float>(),
+                     grid);
   ROC_HIP_CHECK(hipGetLastError());
 }

@@ -1920,6 +1920,23 @@ def decode_metrics(metrics: torch.Tensor) -> dict:
 
 
 # ---------------------------------------------------------------------------
+# Input-row gather of the sampled tier (not autograd — inputs need no grad)
+# ---------------------------------------------------------------------------
+
+def gather_rows_cast(feats, ids, out_dtype=None):
+    """out[j, :] = feats[ids[j], :] in out_dtype (default: feats' own):
+    fp32 -> fp32 / bf16 or bf16 -> bf16, cast in the store (sample.hip).
+    One pass over HBM-resident features instead of index, copy and cast."""
+    out_dtype = feats.dtype if out_dtype is None else out_dtype
+    if _hip(feats):
+        out = torch.empty((ids.numel(), feats.shape[1]), dtype=out_dtype,
+                          device=feats.device)
+        _C.gather_rows_cast(out, feats, ids)
+        return out
+    return feats[ids].to(out_dtype)
+
+
+# ---------------------------------------------------------------------------
 # Adam (not autograd — called by the optimizer)
 # ---------------------------------------------------------------------------
 

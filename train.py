@@ -136,6 +136,11 @@ def parse_args():
                          "GraphSAGE only, world_size=1")
     ap.add_argument("--batch-size", type=int, default=1024,
                     help="target nodes per sampled mini-batch")
+    ap.add_argument("--sampler", choices=["host", "device"], default="host",
+                    help="where --sample builds its blocks: 'host' (OpenMP "
+                         "sampler, host-resident features) or 'device' "
+                         "(HIP sampler over an HBM-resident graph and "
+                         "features; falls back to host on a CPU device)")
     ap.add_argument("--log-csv", default=None,
                     help="append one CSV row per eval (epoch, losses, "
                          "accuracies, ms/epoch); rank 0 only")
@@ -343,7 +348,8 @@ def main():
                               fanouts=fanouts, batch_size=args.batch_size,
                               device=device, compute_dtype=dtype,
                               seed=args.seed, num_classes=num_classes
-                              if dims[-1] != num_classes else None)
+                              if dims[-1] != num_classes else None,
+                              sampler=args.sampler)
         import time as _time
         t0 = _time.perf_counter()
         for ep in range(1, args.epochs + 1):
