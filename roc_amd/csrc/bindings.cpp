@@ -83,6 +83,23 @@ void seg_softmax_bwd(torch::Tensor dx, c10::optional<torch::Tensor> dt_out,
                      torch::Tensor t, torch::Tensor t_rowptr,
                      torch::Tensor t_colidx,
                      c10::optional<torch::Tensor> t_row_order, int64_t depth);
+void gated_agg_fwd(torch::Tensor out, c10::optional<torch::Tensor> stats,
+                   torch::Tensor q, torch::Tensor kv, torch::Tensor rowptr,
+                   torch::Tensor colidx,
+                   c10::optional<torch::Tensor> row_order, bool normalize,
+                   double eps, int64_t depth);
+void gated_agg_bwd_dst(torch::Tensor dq, torch::Tensor dy,
+                       c10::optional<torch::Tensor> stats, torch::Tensor q,
+                       torch::Tensor kv, torch::Tensor rowptr,
+                       torch::Tensor colidx,
+                       c10::optional<torch::Tensor> row_order, bool normalize,
+                       int64_t depth);
+void gated_agg_bwd_src(torch::Tensor dkv, torch::Tensor dy,
+                       c10::optional<torch::Tensor> stats, torch::Tensor q,
+                       torch::Tensor kv, torch::Tensor t_rowptr,
+                       torch::Tensor t_colidx,
+                       c10::optional<torch::Tensor> t_row_order,
+                       bool normalize, int64_t depth);
 void layer_norm_fwd(torch::Tensor y, c10::optional<torch::Tensor> mean,
                     c10::optional<torch::Tensor> rstd, torch::Tensor x,
                     torch::Tensor gamma, torch::Tensor beta, double eps,
@@ -303,6 +320,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("t_rowptr"), pybind11::arg("t_colidx"),
         pybind11::arg("t_row_order") = pybind11::none(),
         pybind11::arg("depth") = 0);
+  m.def("gated_agg_fwd", &gated_agg_fwd,
+        "edge-gated aggregation: out = sum_e sigmoid(q[v] + k[u_e]) * "
+        "val[u_e] over kv = [k | val], divided by (sum_e gate + eps) when "
+        "normalize; stats = fp32 [den | out32] (mean form only), None skips "
+        "its stores",
+        pybind11::arg("out"), pybind11::arg("stats"), pybind11::arg("q"),
+        pybind11::arg("kv"), pybind11::arg("rowptr"), pybind11::arg("colidx"),
+        pybind11::arg("row_order"), pybind11::arg("normalize"),
+        pybind11::arg("eps"), pybind11::arg("depth") = 0);
+  m.def("gated_agg_bwd_dst", &gated_agg_bwd_dst,
+        "gated aggregation gradient, destination-major pass: dq; stats is "
+        "the forward's in the mean form and None in the sum form",
+        pybind11::arg("dq"), pybind11::arg("dy"), pybind11::arg("stats"),
+        pybind11::arg("q"), pybind11::arg("kv"), pybind11::arg("rowptr"),
+        pybind11::arg("colidx"), pybind11::arg("row_order"),
+        pybind11::arg("normalize"), pybind11::arg("depth") = 0);
+  m.def("gated_agg_bwd_src", &gated_agg_bwd_src,
+        "gated aggregation gradient, source-major pass over the transpose "
+        "CSR: dkv = [dk | dval]",
+        pybind11::arg("dkv"), pybind11::arg("dy"), pybind11::arg("stats"),
+        pybind11::arg("q"), pybind11::arg("kv"), pybind11::arg("t_rowptr"),
+        pybind11::arg("t_colidx"), pybind11::arg("t_row_order"),
+        pybind11::arg("normalize"), pybind11::arg("depth") = 0);
   m.def("layer_norm_fwd", &layer_norm_fwd,
         "per-row LayerNorm (+ReLU); mean = rstd = None skips the stats stores",
         pybind11::arg("y"), pybind11::arg("mean"), pybind11::arg("rstd"),

@@ -8,6 +8,7 @@ from .sgc import SGC
 from .appnp import APPNP
 from .pna import PNA, pna_delta
 from .deepergcn import DeeperGCN
+from .gatedgcn import GatedGCN
 
 
 def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
@@ -32,4 +33,6 @@ def build_model(name: str, dims, dropout: float = 0.5, seed: int = 1, **kw):
         return PNA(dims, dropout=dropout, seed=seed, **kw)
     if name == "deepergcn":
         return DeeperGCN(dims, dropout=dropout, seed=seed, **kw)
+    if name == "gatedgcn":
+        return GatedGCN(dims, dropout=dropout, seed=seed, **kw)
     raise ValueError(f"unknown model {name!r}")

@@ -1277,6 +1277,115 @@ def gatv2_attention(xl, xr, att, shard, heads: int, slope: float = 0.2):
 
 
 # ---------------------------------------------------------------------------
+# Edge-gated aggregation (fused per-column sigmoid-gate kernels)
+# ---------------------------------------------------------------------------
+
+class _GatedAggregate(torch.autograd.Function):
+    """GPU path of gated_aggregate (gated_agg.hip). In the mean form the
+    forward saves stats, fp32 [den | out32]: the backward never sees the
+    rounded out. The sum form saves nothing. The backward is two gather
+    passes that recompute the gates: destination-major for dq, source-major
+    over the transpose CSR for dkv, each skipped when its input needs no
+    gradient. No [E, D] tensor, no atomics. need_stats is False when nothing
+    needs a gradient (decided by the caller: grad mode is always off in
+    here); the kernel variant without the state stores runs then."""
+
+    @staticmethod
+    def forward(ctx, q, kv, rowptr, colidx, t_rowptr, t_colidx, normalize,
+                eps, row_order, t_row_order, need_stats):
+        out = torch.empty_like(q)
+        stats = None
+        if need_stats and normalize:
+            stats = torch.empty(q.shape[0], 2 * q.shape[1],
+                                dtype=torch.float32, device=q.device)
+        _C.gated_agg_fwd(out, stats, q, kv, rowptr, colidx, row_order,
+                         normalize, eps)
+        if need_stats:
+            # stats is None in the sum form; save_for_backward takes it
+            ctx.save_for_backward(q, kv, stats, rowptr, colidx, t_rowptr,
+                                  t_colidx, row_order, t_row_order)
+        ctx.normalize = normalize
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (q, kv, stats, rowptr, colidx, t_rowptr, t_colidx, row_order,
+         t_row_order) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dq = dkv = None
+        if ctx.needs_input_grad[0]:
+            dq = torch.empty_like(q)
+            _C.gated_agg_bwd_dst(dq, dy, stats, q, kv, rowptr, colidx,
+                                 row_order, ctx.normalize)
+        if ctx.needs_input_grad[1]:
+            dkv = torch.empty_like(kv)
+            _C.gated_agg_bwd_src(dkv, dy, stats, q, kv, t_rowptr, t_colidx,
+                                 t_row_order, ctx.normalize)
+        return (dq, dkv) + (None,) * 9
+
+
+def gated_aggregate_csr(q, kv, rowptr, colidx, t_rowptr, t_colidx, num_rows,
+                        num_src, normalize: bool = True, eps: float = 1e-6,
+                        row_order=None, t_row_order=None):
+    """gated_aggregate over an explicit CSR / transpose-CSR pair. Every
+    argument is checked here, before any launch."""
+    if q.dim() != 2 or q.shape[0] != num_rows:
+        raise ValueError(f"q must be [{num_rows}, D], got {tuple(q.shape)}")
+    D = q.shape[1]
+    if tuple(kv.shape) != (num_src, 2 * D):
+        # colidx indexes kv unchecked on the GPU: a short kv reads out of
+        # bounds
+        raise ValueError(
+            f"kv must be [{num_src}, {2 * D}], got {tuple(kv.shape)}")
+    if q.dtype != kv.dtype:
+        raise ValueError(
+            f"q and kv must share a dtype, got {q.dtype} and {kv.dtype}")
+    if q.device != kv.device:
+        raise ValueError("q and kv must live on one device")
+    if q.is_cuda and q.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(
+            f"gated_aggregate on GPU takes bf16 or fp32, got {q.dtype}")
+    normalize, eps = bool(normalize), float(eps)
+    if normalize and not eps > 0.0:
+        # a row whose gates all underflow has a zero gate sum
+        raise ValueError(f"the mean form needs eps > 0, got {eps}")
+    if int(colidx.numel()) >= 2 ** 31:
+        raise ValueError("2^31 or more edges do not fit the int32 edge index")
+    if not _hip(q):
+        return ref.gated_aggregate(q, kv, rowptr, colidx, num_rows, normalize,
+                                   eps)
+    need_stats = torch.is_grad_enabled() and (q.requires_grad
+                                              or kv.requires_grad)
+    return _GatedAggregate.apply(
+        q.contiguous(), kv.contiguous(), rowptr, colidx, t_rowptr, t_colidx,
+        normalize, eps, row_order, t_row_order, need_stats)
+
+
+def gated_aggregate(q, kv, shard, normalize: bool = True, eps: float = 1e-6):
+    """Edge-gated aggregation over each node's in-neighbourhood (Bresson &
+    Laurent's residual gated graph ConvNet, PyG's ResGatedGraphConv).
+
+    q: [n_local, D], the destination projection. kv: [n_ext, 2*D],
+    halo-extended, the gate's source half k in columns [0, D) and the
+    values in [D, 2D): one projection GEMM and one halo exchange serve
+    both. For row v, column j and in-edge e from u_e:
+      eta[e, j] = sigmoid(q[v, j] + k[u_e, j])
+      out[v, j] = sum_e eta[e, j] * val[u_e, j]
+    and in the mean form (normalize, the default) that sum divided by
+    sum_e eta[e, j] + eps: a plain gated sum grows with the degree. Returns
+    [n_local, D] in q's dtype (bf16 or fp32 on GPU; all arithmetic is fp32,
+    one rounding at the store). The gate stays finite at any q + k.
+    Duplicate edges each count; a row without edges gives 0 and passes no
+    gradient; a source without out-edges gets a zero gradient. `shard` may
+    be a GraphShard, a sampling Block or anything with the same CSR
+    fields."""
+    return gated_aggregate_csr(
+        q, kv, shard.rowptr, shard.colidx, shard.t_rowptr, shard.t_colidx,
+        shard.n_local, shard.n_ext, normalize, eps, shard.row_order,
+        shard.t_row_order)
+
+
+# ---------------------------------------------------------------------------
 # InDegreeNorm
 # ---------------------------------------------------------------------------
 

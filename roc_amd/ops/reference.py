@@ -291,6 +291,34 @@ def seg_softmax_grad(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor,
     return dx.to(dy.dtype), (w * d * d).sum().reshape(1)
 
 
+def gated_aggregate(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
+                    colidx: torch.Tensor, num_rows: int,
+                    normalize: bool = True, eps: float = 1e-6) -> torch.Tensor:
+    """Edge-gated aggregation (Bresson & Laurent's residual gated graph
+    ConvNet, PyG's ResGatedGraphConv; the reference has no such layer): for
+    the edges e = (v <- u_e) of row v and every column j,
+      eta[e, j] = sigmoid(q[v, j] + k[u_e, j])
+      out[v, j] = sum_e eta[e, j] * val[u_e, j]        / (sum_e eta[e, j] + eps)
+    with the division in the mean form (normalize) only. q: [num_rows, D];
+    kv: [n_src, 2*D] with k in columns [0, D) and val in [D, 2D). Duplicate
+    edges each count; a row without edges gives 0. Index ops in fp32 (fp64
+    stays fp64), differentiable by autograd; the result is cast back to q's
+    dtype."""
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    D = q.shape[1]
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.long)
+    dst = torch.repeat_interleave(
+        torch.arange(num_rows, dtype=torch.long, device=q.device), deg)
+    src = colidx.to(torch.long)
+    k, val = kv.to(ct).split(D, 1)
+    eta = torch.sigmoid(q.to(ct)[dst] + k[src])                  # [E, D]
+    zeros = torch.zeros(num_rows, D, dtype=ct, device=q.device)
+    out = zeros.index_add(0, dst, eta * val[src])
+    if normalize:
+        out = out / (zeros.index_add(0, dst, eta) + eps)
+    return out.to(q.dtype)
+
+
 def graph_attention(q: torch.Tensor, kv: torch.Tensor, rowptr: torch.Tensor,
                     colidx: torch.Tensor, num_rows: int, heads: int,
                     scale: float) -> torch.Tensor:

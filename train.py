@@ -10,7 +10,8 @@ Multi GPU (one process per GPU, RCCL):
 Reference flag parity: --file (.lux dataset prefix), --layers D0-D1-...-C,
 --epochs, --lr, --weight-decay, --decay-rate, --decay-steps, --dropout,
 --seed; metrics printed every 5 epochs (`gnn.cc:107-110`). New:
---model gcn|sage|gin|gat|gatv2|transformer|pna|deepergcn, --norm none|layer|batch,
+--model gcn|sage|gin|gat|gatv2|transformer|pna|deepergcn|gatedgcn,
+--norm none|layer|batch,
 --edge-drop P, --dtype,
 --checkpoint/--resume, --trace.
 """
@@ -47,16 +48,17 @@ def parse_args():
                          "e.g. 602-256-41")
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--num-layers", type=int, default=2)
-    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "gatv2", "transformer", "pna", "deepergcn", "sgc",
-                             "appnp"])
+    ap.add_argument("--model", default="gcn", choices=["gcn", "sage", "gin", "gat", "gatv2", "transformer", "pna", "deepergcn", "gatedgcn",
+                             "sgc", "appnp"])
     ap.add_argument("--aggr", default="mean", choices=["mean", "max", "min"],
                     help="neighbor aggregation of --model sage: mean, or "
                          "the elementwise max / min over in-neighbors")
     ap.add_argument("--norm", default="none", choices=["none", "layer", "batch"],
                     help="hidden-layer normalization of --model gcn, sage, "
-                         "gin, transformer, gatv2, pna or deepergcn: layer = "
+                         "gin, transformer, gatv2, pna, deepergcn or gatedgcn: "
+                         "layer = "
                          "fused per-node LayerNorm + ReLU; batch (gcn, sage, "
-                         "gin, deepergcn) = "
+                         "gin, deepergcn, gatedgcn) = "
                          "BatchNorm + ReLU over the nodes of all ranks, "
                          "running statistics in eval")
     ap.add_argument("--epochs", "-e", type=int, default=100)
@@ -187,13 +189,15 @@ def parse_args():
     if args.norm not in ("none", "layer", "batch"):  # a YAML value
         ap.error(f"--norm must be none, layer or batch, got {args.norm!r}")
     if args.norm == "batch" and args.model not in ("gcn", "sage", "gin",
-                                                   "deepergcn"):
-        ap.error("--norm batch needs --model gcn, sage, gin or deepergcn")
+                                                   "deepergcn", "gatedgcn"):
+        ap.error("--norm batch needs --model gcn, sage, gin, deepergcn or "
+                 "gatedgcn")
     if args.norm != "none" and args.model not in ("gcn", "sage", "gin",
                                                   "transformer", "gatv2",
-                                                  "pna", "deepergcn"):
+                                                  "pna", "deepergcn",
+                                                  "gatedgcn"):
         ap.error(f"--norm {args.norm} needs --model gcn, sage, gin, "
-                 f"transformer, gatv2, pna or deepergcn: --model "
+                 f"transformer, gatv2, pna, deepergcn or gatedgcn: --model "
                  f"{args.model} has no hidden-layer norm")
     return args
 
